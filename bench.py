@@ -22,6 +22,11 @@ Launch (driver contract):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times exactly --steps steps and prints one
+JSON line. --dump-outputs DIR also writes the last timed step's arrays
+(seeded inputs and weights: identical from run to run); --full is where
+secondary measurements belong (none exist today).
+
 Tensor-parallel mode (BASELINE config 4, Llama-3-70B TP=8 over xGMI):
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
       --master-addr 127.0.0.1 bench.py --gpus 8 --tp 8 --steps K --warmup W
@@ -73,7 +78,69 @@ def parse_args():
     p.add_argument("--dense-quant", default="", choices=["", "fp8", "mxfp4"],
                    help="opt-in quantized dense decode projections (turbo; "
                         "NOT the headline dtype)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed (decode logits, sampled tokens, each "
+                        "agent's latest reply) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements; the plain run "
+                        "is only setup, warmup, the timed steps and the "
+                        "result line (there are none today, so the flag "
+                        "changes nothing yet)")
     return p.parse_args()
+
+
+# --dump-outputs size budget: 64 MB in all; the logits get the lion's share
+DUMP_LOGITS_BYTES = 48 << 20
+
+
+class LastSample:
+    """Keeps the arguments and result of the engine's most recent sampler
+    call. Within one step the decode launch samples last, so after the
+    timed region this holds the last step's decode logits and tokens."""
+
+    def __init__(self, inst):
+        self.logits = None
+        self.tokens = None
+        self._inner = inst._sample_device_params
+        inst._sample_device_params = self
+
+    def __call__(self, logits, temps_l, tops_l, seeds_l):
+        out = self._inner(logits, temps_l, tops_l, seeds_l)
+        self.logits, self.tokens = logits, out
+        return out
+
+
+def dump_outputs(path, rank, last, clients, gen_len):
+    """Write the last timed step's outputs as float32 .npy files. Rank 0
+    writes <name>.npy; further data-parallel ranks add a _rank<r> suffix."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if rank else ""
+
+    def save(name, arr):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"),
+                np.ascontiguousarray(arr, dtype=np.float32))
+
+    if last.logits is not None:
+        logits = last.logits.detach().float().cpu().numpy()
+        if logits.nbytes > DUMP_LOGITS_BYTES:
+            # fixed, seeded column sample of an over-budget logits matrix
+            keep = DUMP_LOGITS_BYTES // (4 * logits.shape[0])
+            cols = np.sort(np.random.default_rng(0).choice(
+                logits.shape[1], size=keep, replace=False))
+            save("last_step_logits_columns", cols)
+            logits = logits[:, cols]
+        save("last_step_logits", logits)
+        save("last_step_tokens", last.tokens.detach().cpu().numpy())
+    # what a chat caller received: each agent's most recent completed reply
+    # (token ids; -1 pads a short or absent reply)
+    replies = np.full((len(clients), gen_len), -1.0, dtype=np.float32)
+    for i, c in enumerate(clients):
+        toks = c.last_reply[:gen_len]
+        replies[i, :len(toks)] = toks
+    save("reply_tokens", replies)
 
 
 class ClosedLoopClient:
@@ -91,6 +158,7 @@ class ClosedLoopClient:
         self.active = None
         self.active_wal = None
         self.completed = []  # (t_submit, t_done)
+        self.last_reply = []  # generated tokens of the latest completion
 
     def _prompt_tokens(self):
         v = self.inst.cfg.vocab_size
@@ -112,6 +180,7 @@ class ClosedLoopClient:
     def poll(self, record: bool):
         if self.active is not None and self.active.done.is_set():
             req = self.active
+            self.last_reply = req.generated
             self.wal.store_response(self.agent.id, self.active_wal.id,
                                     {"tokens": len(req.generated)})
             hist = f"agent:{self.agent.id}:conversations"
@@ -156,11 +225,10 @@ def main():
         model_name = args.model or ("llama3-8b" if has_gpu else "tiny-llama")
     if not has_gpu and args.model is None:
         # CPU fallback sizes so the no-GPU smoke run finishes in seconds
+        # (--steps and --warmup are always honoured as given)
         args.agents = min(args.agents, 4)
         args.prompt_len = min(args.prompt_len, 32)
         args.gen_len = min(args.gen_len, 8)
-        args.steps = min(args.steps, 40)
-        args.warmup = min(args.warmup, 8)
     # any driver-chosen --steps must complete requests INSIDE the timed
     # region (a gen_len longer than the window yields a vacuous 0 req/s):
     # cap generation length at half the timed steps
@@ -217,6 +285,7 @@ def main():
                for i, a in enumerate(agents)]
     for c in clients:
         c.submit()
+    last = LastSample(inst) if args.dump_outputs else None
 
     def run_steps(n, record):
         for _ in range(n):
@@ -241,6 +310,8 @@ def main():
     e2es = sorted(d - s for c in clients for (s, d) in c.completed)
     decode_tokens = inst.decode_tokens
     prefill_tokens = inst.prefill_tokens
+    if last is not None:
+        dump_outputs(args.dump_outputs, rank, last, clients, args.gen_len)
 
     if dist and tp == 1:
         # weak DP: whole-job aggregate = sum of completions / MAX elapsed,

@@ -55,6 +55,49 @@ def test_bench_single_process_contract():
 
 
 @pytest.mark.timeout(300)
+def test_bench_dump_outputs_reproducible(tmp_path):
+    """--dump-outputs writes the last timed step's arrays as float .npy
+    files (<= 64 MB in all), identical from run to run for the same
+    arguments; --steps is the number of timed steps; --full is accepted."""
+    import numpy as np
+
+    dumps = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, "bench.py", "--gpus", "1",
+                            "--steps", "50", "--warmup", "9",
+                            "--dump-outputs", str(d)] + extra,
+                           capture_output=True, text=True, cwd=ROOT,
+                           timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _last_json_line(r.stdout)
+        # above the old CPU caps (40 / 8): the request is honoured as given
+        assert out["steps"] == 50 and out["warmup"] == 9
+        assert out["ms_per_step"] > 0
+        dumps.append({p.name: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"last_step_logits.npy", "last_step_tokens.npy",
+            "reply_tokens.npy"} <= set(a)
+    assert set(a) == set(b)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        assert np.array_equal(a[k], b[k]), k
+    n_agents, vocab = a["last_step_logits.npy"].shape
+    assert a["last_step_tokens.npy"].shape == (n_agents,)
+    assert np.isfinite(a["last_step_logits.npy"]).all()
+    # greedy decode: the dumped tokens are the argmax of the dumped logits
+    # (the sampler reads them as bf16; ties are compared by value)
+    import torch
+
+    lg = torch.from_numpy(a["last_step_logits.npy"]).to(
+        torch.bfloat16).float().numpy()
+    tk = a["last_step_tokens.npy"].astype(np.int64)
+    assert np.array_equal(lg[np.arange(n_agents), tk], lg.max(axis=1))
+    assert (a["reply_tokens.npy"] >= 0).any()
+
+
+@pytest.mark.timeout(300)
 def test_bench_driver_r1_shape_nonzero():
     """The EXACT launch shape whose round-1 record carried value=0.0
     (driver ran --steps 20 --warmup 5 against gen_len=64)."""
