@@ -96,7 +96,11 @@ class LlamaAttention(torch.nn.Module):
         self.qkv_q = None
         self.o_q = None
 
-    def forward(self, h, k_cache, v_cache, md: AttnMetadata, cos_sin, tp_group=None):
+    def forward(self, h, k_cache, v_cache, md: AttnMetadata, cos_sin,
+                tp_group=None, defer_reduce: bool = False):
+        """defer_reduce: the caller feeds the result straight into
+        ops.fused_add_rmsnorm, so a split-K o-proj may come back as an
+        ops.SplitKPartial (never under TP: the all-reduce needs bf16)."""
         T = h.size(0)
         if self.qkv_q is not None and T <= 64 and h.is_cuda:
             qkv = ops.linear_quant(h, self.qkv_q)
@@ -125,6 +129,9 @@ class LlamaAttention(torch.nn.Module):
                                        md.seq_lens, self.scale)
         if self.o_q is not None and T <= 64 and h.is_cuda:
             o = ops.linear_quant(out.view(T, q_sz), self.o_q)
+        elif defer_reduce and tp_group is None:
+            o = ops.linear_partial(out.view(T, q_sz), self.o_proj,
+                                   self.o_packed)
         else:
             o = ops.linear(out.view(T, q_sz), self.o_proj, self.o_packed)
         if tp_group is not None:
@@ -146,7 +153,8 @@ class LlamaMLP(torch.nn.Module):
         self.gate_up_q = None
         self.down_q = None
 
-    def forward(self, h, tp_group=None):
+    def forward(self, h, tp_group=None, defer_reduce: bool = False):
+        # defer_reduce: as in LlamaAttention.forward, for the down-proj
         turbo = self.gate_up_q is not None and h.size(0) <= 64 and h.is_cuda
         if turbo:
             gu = ops.linear_quant(h, self.gate_up_q)
@@ -158,6 +166,8 @@ class LlamaMLP(torch.nn.Module):
         ops.silu_mul(act, gate, up)
         if turbo:
             out = ops.linear_quant(act, self.down_q)
+        elif defer_reduce and tp_group is None:
+            out = ops.linear_partial(act, self.down, self.down_packed)
         else:
             out = ops.linear(act, self.down, self.down_packed)
         if tp_group is not None:
@@ -174,17 +184,23 @@ class LlamaLayer(torch.nn.Module):
         self.post_ln = torch.nn.Parameter(torch.empty(cfg.hidden_size, dtype=torch.bfloat16))
         self.eps = cfg.norm_eps
 
-    def forward(self, hidden, residual, k_cache, v_cache, md, cos_sin, tp_group=None):
-        normed = torch.empty_like(hidden)
+    def forward(self, hidden, residual, k_cache, v_cache, md, cos_sin,
+                tp_group=None, defer_reduce: bool = False):
+        """hidden may be the previous layer's ops.SplitKPartial; with
+        defer_reduce the returned mlp_out may be one too (the caller's next
+        fused_add_rmsnorm reduces it)."""
         if residual is None:
+            normed = torch.empty_like(hidden)
             residual = hidden.clone()
             ops.rmsnorm(normed, hidden, self.input_ln, self.eps)
         else:
+            normed = torch.empty_like(residual)
             ops.fused_add_rmsnorm(normed, hidden, residual, self.input_ln, self.eps)
-        attn_out = self.attn(normed, k_cache, v_cache, md, cos_sin, tp_group)
-        normed2 = torch.empty_like(hidden)
+        attn_out = self.attn(normed, k_cache, v_cache, md, cos_sin, tp_group,
+                             defer_reduce=True)
+        normed2 = torch.empty_like(residual)
         ops.fused_add_rmsnorm(normed2, attn_out, residual, self.post_ln, self.eps)
-        mlp_out = self.mlp(normed2, tp_group)
+        mlp_out = self.mlp(normed2, tp_group, defer_reduce=defer_reduce)
         return mlp_out, residual
 
 
@@ -237,8 +253,9 @@ class LlamaForCausalLM(torch.nn.Module):
         for i, layer in enumerate(self.layers):
             k_cache, v_cache = kv_caches[i]
             hidden, residual = layer(hidden, residual, k_cache, v_cache, md,
-                                     self.cos_sin, self.tp_group)
-        final = torch.empty_like(hidden)
+                                     self.cos_sin, self.tp_group,
+                                     defer_reduce=True)
+        final = torch.empty_like(residual)
         ops.fused_add_rmsnorm(final, hidden, residual, self.final_ln, self.cfg.norm_eps)
         if last_rows is not None:
             final = final[last_rows]

@@ -297,7 +297,10 @@ class MixtralLayer(torch.nn.Module):
             ops.rmsnorm(normed, hidden, self.input_ln, self.eps)
         else:
             ops.fused_add_rmsnorm(normed, hidden, residual, self.input_ln, self.eps)
-        attn_out = self.attn(normed, k_cache, v_cache, md, cos_sin, tp_group)
+        # post_ln is the o-proj's only consumer: it may reduce the split-K
+        # partials itself (ops.SplitKPartial)
+        attn_out = self.attn(normed, k_cache, v_cache, md, cos_sin, tp_group,
+                             defer_reduce=True)
         normed2 = torch.empty_like(hidden)
         ops.fused_add_rmsnorm(normed2, attn_out, residual, self.post_ln, self.eps)
         moe_out = self.moe(normed2, ep_group=tp_group)

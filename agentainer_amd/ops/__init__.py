@@ -70,6 +70,14 @@ def rmsnorm(out, x, w, eps: float = 1e-5):
 
 
 def fused_add_rmsnorm(out, x, residual, w, eps: float = 1e-5):
+    """residual += x; out = rmsnorm(residual) * w. x is a tensor, or the
+    SplitKPartial that linear_partial returned: the norm kernel then sums
+    the GEMM's split-K partials itself (bit-identical to combining first)."""
+    if isinstance(x, SplitKPartial):
+        mod = _dispatch("splitk_add_rmsnorm", residual)
+        mod.splitk_add_rmsnorm(out, x.consume(), x.split, x.M, x.N, residual,
+                               w, float(eps))
+        return out
     mod = _dispatch("fused_add_rmsnorm", x)
     if mod:
         mod.fused_add_rmsnorm(out, x, residual, w, float(eps))
@@ -167,6 +175,9 @@ _ws_cache = {}
 _EMPTY_WS = {}
 SKINNY_DISABLED = os.environ.get("AGENTAINER_DISABLE_SKINNY", "0") == "1"
 SKINNY_FORCED = os.environ.get("AGENTAINER_FORCE_SKINNY", "0") == "1"
+# A/B hook: linear_partial always combines (no deferred split-K reduction)
+SPLITK_DEFER_DISABLED = (
+    os.environ.get("AGENTAINER_DISABLE_SPLITK_DEFER", "0") == "1")
 # shapes where the hand-written skinny GEMM beat hipBLASLt on MI355X,
 # with the (split_k, k_chunk) that won the tools/sg_sweep.py grid
 # (M=64; see profiles/README.md). Library keeps qkv/gate_up: at
@@ -203,14 +214,53 @@ def pack_weight(w: torch.Tensor) -> torch.Tensor:
     return p.view(-1)
 
 
+class _Workspace:
+    """One cached split-K buffer; gen counts how often it was handed out."""
+    __slots__ = ("buf", "gen")
+
+    def __init__(self, buf: torch.Tensor):
+        self.buf = buf
+        self.gen = 0
+
+
+class SplitKPartial:
+    """A skinny GEMM's result still in split-K form: ws holds the f32
+    partials [split, M, N], to be summed by the consumer
+    (fused_add_rmsnorm). It borrows a cached workspace, so it must be
+    consumed before that workspace is handed out again — consume() raises
+    otherwise instead of reading another GEMM's partials."""
+    __slots__ = ("ws", "split", "M", "N", "_slot", "_gen")
+
+    def __init__(self, slot: _Workspace, split: int, M: int, N: int):
+        self.ws, self.split, self.M, self.N = slot.buf, split, M, N
+        self._slot, self._gen = slot, slot.gen
+
+    def consume(self) -> torch.Tensor:
+        if self._slot.gen != self._gen or self._slot.buf is not self.ws:
+            raise RuntimeError(
+                "stale SplitKPartial: its split-K workspace was handed out "
+                "again before the partials were consumed")
+        return self.ws
+
+
+def _skinny_ws_slot(device, N: int, split: int) -> _Workspace:
+    # keyed by the current stream too: a side-stream prefill with <= 64
+    # padded tokens takes the skinny path and must not write the buffer an
+    # in-flight decode graph on another stream is still reading
+    stream = torch.cuda.current_stream(device).cuda_stream
+    key = (device, stream, N, split)
+    slot = _ws_cache.get(key)
+    if slot is None or slot.buf.numel() < split * 64 * N:
+        slot = _Workspace(torch.empty(split * 64 * N, dtype=torch.float32,
+                                      device=device))
+        _ws_cache[key] = slot
+    slot.gen += 1
+    return slot
+
+
 def _skinny_ws(device, N: int, split: int) -> torch.Tensor:
     if split > 1:
-        key = (device, N, split)
-        ws = _ws_cache.get(key)
-        if ws is None or ws.numel() < split * 64 * N:
-            ws = torch.empty(split * 64 * N, dtype=torch.float32, device=device)
-            _ws_cache[key] = ws
-        return ws
+        return _skinny_ws_slot(device, N, split).buf
     ws = _EMPTY_WS.get(device)
     if ws is None:
         ws = torch.empty(1, dtype=torch.float32, device=device)
@@ -224,6 +274,19 @@ def linear(x: torch.Tensor, w: torch.Tensor,
     hand-written skinny MFMA kernel — packed-weight variant when the
     caller pre-packed W (streams at the HBM roofline); everything else to
     hipBLASLt via F.linear."""
+    return _linear(x, w, w_packed, False)
+
+
+def linear_partial(x: torch.Tensor, w: torch.Tensor,
+                   w_packed: Optional[torch.Tensor] = None):
+    """linear() for a result whose only consumer is fused_add_rmsnorm:
+    same dispatch, but a split-K skinny GEMM skips its combine launch and
+    returns a SplitKPartial for the norm to reduce. Everything else (CPU,
+    hipBLASLt, split 1, SPLITK_DEFER_DISABLED) returns the bf16 tensor."""
+    return _linear(x, w, w_packed, not SPLITK_DEFER_DISABLED)
+
+
+def _linear(x, w, w_packed, defer: bool):
     M, K = x.shape
     N = w.size(0)
     tuned = _SKINNY_SHAPES.get((N, K))
@@ -235,14 +298,20 @@ def linear(x: torch.Tensor, w: torch.Tensor,
             kc = SKINNY_KC
         if K % (kc * split):
             split = _skinny_split(N // 64, K)
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        ws = _skinny_ws(x.device, N, split)
+        defer = defer and split > 1 and M >= 1
+        if defer:
+            slot = _skinny_ws_slot(x.device, N, split)
+            ws = slot.buf
+            out = torch.empty(0, dtype=x.dtype, device=x.device)  # unwritten
+        else:
+            ws = _skinny_ws(x.device, N, split)
+            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
         if w_packed is not None:
             mod.skinny_gemm_packed(out, x.contiguous(), w_packed, N, K, ws,
-                                   split, SKINNY_NT, kc)
+                                   split, SKINNY_NT, kc, not defer)
         else:
-            mod.skinny_gemm(out, x.contiguous(), w, ws, split)
-        return out
+            mod.skinny_gemm(out, x.contiguous(), w, ws, split, not defer)
+        return SplitKPartial(slot, split, M, N) if defer else out
     return torch.nn.functional.linear(x, w)
 
 

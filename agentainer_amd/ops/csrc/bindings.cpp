@@ -28,10 +28,14 @@ void topp_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temps,
 void gather_kv_pages(torch::Tensor dst, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor page_ids);
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                 torch::Tensor ws, long split);
+                 torch::Tensor ws, long split, bool combine);
 void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
                         torch::Tensor w_packed, long N, long K,
-                        torch::Tensor ws, long split, bool nt, long kc);
+                        torch::Tensor ws, long split, bool nt, long kc,
+                        bool combine);
+void splitk_add_rmsnorm(torch::Tensor out, torch::Tensor ws, long split,
+                        long M, long N, torch::Tensor residual,
+                        torch::Tensor w, double eps);
 void quant_fp8_rows(torch::Tensor x8, torch::Tensor sx, torch::Tensor x);
 void quant_fp4_rows(torch::Tensor x4, torch::Tensor sx, torch::Tensor x);
 void skinny_gemm_mxfp4(torch::Tensor out, torch::Tensor x8, torch::Tensor sx,
@@ -59,8 +63,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("greedy_sample", &greedy_sample, "argmax over vocab per row");
   m.def("topp_sample", &topp_sample, "temperature + top-p sampling per row");
   m.def("gather_kv_pages", &gather_kv_pages, "pages -> host-shaped buffer");
-  m.def("skinny_gemm", &skinny_gemm, "out[M,N] = x[M,K] @ W[N,K]^T, M<=64");
-  m.def("skinny_gemm_packed", &skinny_gemm_packed, "packed-weight skinny GEMM");
+  m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm,
+        "residual += bf16(sum_s ws[s]); rmsnorm");
+  // combine=False leaves the split-K partials in ws (no combine launch)
+  m.def("skinny_gemm", &skinny_gemm, "out[M,N] = x[M,K] @ W[N,K]^T, M<=64",
+        py::arg("out"), py::arg("x"), py::arg("w"), py::arg("ws"),
+        py::arg("split"), py::arg("combine") = true);
+  m.def("skinny_gemm_packed", &skinny_gemm_packed, "packed-weight skinny GEMM",
+        py::arg("out"), py::arg("x"), py::arg("w_packed"), py::arg("N"),
+        py::arg("K"), py::arg("ws"), py::arg("split"), py::arg("nt"),
+        py::arg("kc"), py::arg("combine") = true);
   m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4, "MXFP4 block-scaled expert GEMM");
   m.def("quant_fp4_rows", &quant_fp4_rows, "per-row e2m1 activation quant");
   m.def("quant_fp8_rows", &quant_fp8_rows, "per-row bf16 -> e4m3 quant");

@@ -157,8 +157,12 @@ __global__ __launch_bounds__(256) void splitk_combine_kernel(
 
 }  // namespace
 
+// combine=false stops after the split-K GEMM: ws keeps the f32 partials
+// [split, M, N] for a consumer that reduces them itself
+// (splitk_add_rmsnorm) and out is not written. split == 1 has no
+// partials and writes bf16 out either way.
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
-                 torch::Tensor ws, long split) {
+                 torch::Tensor ws, long split, bool combine) {
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous() && out.is_contiguous());
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16);
   const int M = x.size(0), K = x.size(1), N = w.size(0);
@@ -178,6 +182,7 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
                      stream, OUTP, (const short*)x.data_ptr(),                 \
                      (const short*)w.data_ptr(), M, N, K, kps)
   if (split == 1) {
+    TORCH_CHECK(out.numel() >= (long)M * N, "skinny_gemm: out smaller than [M,N]");
     if (full) SG_LAUNCH(false, true, out.data_ptr());
     else SG_LAUNCH(false, false, out.data_ptr());
   } else {
@@ -186,10 +191,14 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
     TORCH_CHECK(ws.scalar_type() == at::kFloat);
     if (full) SG_LAUNCH(true, true, ws.data_ptr());
     else SG_LAUNCH(true, false, ws.data_ptr());
-    const long mn = (long)M * N;
-    hipLaunchKernelGGL(splitk_combine_kernel,
-                       dim3((mn + 1023) / 1024), dim3(256), 0, stream,
-                       (short*)out.data_ptr(), ws.data_ptr<float>(), mn, split);
+    if (combine) {
+      const long mn = (long)M * N;
+      TORCH_CHECK(out.numel() >= mn, "skinny_gemm: out smaller than [M,N]");
+      hipLaunchKernelGGL(splitk_combine_kernel,
+                         dim3((mn + 1023) / 1024), dim3(256), 0, stream,
+                         (short*)out.data_ptr(), ws.data_ptr<float>(), mn,
+                         split);
+    }
   }
 #undef SG_LAUNCH
 }
@@ -338,7 +347,8 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
 
 void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
                         torch::Tensor w_packed, long N, long K,
-                        torch::Tensor ws, long split, bool nt, long kc) {
+                        torch::Tensor ws, long split, bool nt, long kc,
+                        bool combine) {
   TORCH_CHECK(x.is_contiguous() && w_packed.is_contiguous() && out.is_contiguous());
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
               w_packed.scalar_type() == at::kBFloat16);
@@ -371,14 +381,20 @@ void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
     else SGP_KC(SPLIT_, false, false, OUTP);                                   \
   } while (0)
   if (split == 1) {
+    TORCH_CHECK(out.numel() >= (long)M * N,
+                "skinny_gemm_packed: out smaller than [M,N]");
     SGP_DISPATCH(false, out.data_ptr());
   } else {
     TORCH_CHECK(ws.numel() >= (long)split * M * N && ws.scalar_type() == at::kFloat);
     SGP_DISPATCH(true, ws.data_ptr());
-    const long mn = (long)M * N;
-    hipLaunchKernelGGL(splitk_combine_kernel, dim3((mn + 1023) / 1024),
-                       dim3(256), 0, stream, (short*)out.data_ptr(),
-                       ws.data_ptr<float>(), mn, split);
+    if (combine) {
+      const long mn = (long)M * N;
+      TORCH_CHECK(out.numel() >= mn,
+                  "skinny_gemm_packed: out smaller than [M,N]");
+      hipLaunchKernelGGL(splitk_combine_kernel, dim3((mn + 1023) / 1024),
+                         dim3(256), 0, stream, (short*)out.data_ptr(),
+                         ws.data_ptr<float>(), mn, split);
+    }
   }
 #undef SGP_DISPATCH
 #undef SGP_LAUNCH
