@@ -189,6 +189,7 @@ def create_app(rt: Runtime) -> FastAPI:
                 token=body.get("token"),
                 health_check=body.get("health_check"),
                 system_prompt=body.get("system_prompt", ""),
+                lora=str(body.get("lora") or ""),
                 sampling=body.get("sampling") or {},
             ))
         cl = _client(request)

@@ -109,6 +109,7 @@ class BackupManager:
                 token=cfg.get("token"),
                 health_check=cfg.get("health_check"),
                 system_prompt=cfg.get("system_prompt", ""),
+                lora=cfg.get("lora", ""),
                 sampling=cfg.get("sampling") or {},
             )
             for conv in entry.get("conversations", []):

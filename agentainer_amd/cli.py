@@ -113,9 +113,12 @@ def server(host, port, config_path, engine_device):
 @click.option("--auto-restart", is_flag=True)
 @click.option("--token", "agent_token", default=None, help="per-agent token")
 @click.option("--system-prompt", default="")
+@click.option("--lora", "lora_path", default="",
+              help="LoRA adapter directory (needs engine.lora_slots > 0)")
 @pass_client
 def deploy(client: Client, model, name, config_path, dtype, tp_degree, kv_budget,
-           max_context, env_kv, auto_restart, agent_token, system_prompt):
+           max_context, env_kv, auto_restart, agent_token, system_prompt,
+           lora_path):
     """Deploy agent(s): MODEL is a family id (e.g. llama3-8b) or weights path."""
     from .config.deployment import parse_memory
 
@@ -135,7 +138,7 @@ def deploy(client: Client, model, name, config_path, dtype, tp_degree, kv_budget
         "model": model, "dtype": dtype, "tp_degree": tp_degree,
         "kv_budget": parse_memory(kv_budget), "max_context": max_context,
         "env": env, "auto_restart": auto_restart, "token": agent_token,
-        "system_prompt": system_prompt,
+        "system_prompt": system_prompt, "lora": lora_path,
     })
     a = resp.get("data") or {}
     click.echo(f"deployed {a.get('name')} -> {a.get('id')}")

@@ -52,6 +52,8 @@ DEFAULTS: Dict[str, Dict[str, Any]] = {
         "expert_fp8": False,       # e4m3 Mixtral expert GEMMs
         "expert_fp4": False,       # MXFP4 Mixtral expert GEMMs
         "tp_degree": 1,
+        "lora_slots": 0,           # resident per-agent LoRA adapters; 0 = off
+        "lora_max_rank": 16,       # largest adapter r (fused qkv pool R = 3r <= 64)
     },
     "security": {
         "api_token": DEFAULT_TOKEN,

@@ -59,6 +59,7 @@ class AgentSpec:
     token: Optional[str] = None
     health_check: Optional[Dict[str, Any]] = None
     system_prompt: str = ""
+    lora: str = ""               # LoRA adapter directory; "" = base model
     sampling: Dict[str, Any] = field(default_factory=dict)  # temperature/top_p/top_k/max_tokens
     dependencies: List[str] = field(default_factory=list)
 
@@ -69,7 +70,7 @@ class AgentSpec:
             "max_context": self.max_context, "env": self.env,
             "auto_restart": self.auto_restart, "token": self.token,
             "health_check": self.health_check, "system_prompt": self.system_prompt,
-            "sampling": self.sampling, "dependencies": self.dependencies,
+            "lora": self.lora, "sampling": self.sampling, "dependencies": self.dependencies,
         }
 
 
@@ -115,6 +116,7 @@ def load_deployment(path: str) -> List[AgentSpec]:
             token=a.get("token"),
             health_check=a.get("healthCheck", a.get("health_check")),
             system_prompt=a.get("systemPrompt", a.get("system_prompt", "")),
+            lora=str(a.get("lora") or ""),
             sampling=dict(a.get("sampling") or {}),
             dependencies=deps,
         )

@@ -9,11 +9,35 @@ stub (BASELINE.json config 1, CPU) and the LLM engine (configs 2-5, MI355X).
 
 from __future__ import annotations
 
+import json
+import os
 from typing import Any, Dict, List, Protocol, runtime_checkable
 
 
 class ModelNotFound(Exception):
     """Analog of deploy's image-must-exist failure (reference agent.go:106-112)."""
+
+
+class AdapterNotFound(ModelNotFound):
+    """Deploy named a LoRA adapter directory that is missing or unreadable."""
+
+
+def validate_adapter_dir(path: str) -> Dict[str, Any]:
+    """Deploy-time check of an agent's `lora` field: the directory exists
+    and its adapter_config.json parses. Returns the parsed config. Shapes
+    are checked against the base model when the adapter is loaded."""
+    p = os.path.abspath(os.path.expanduser(path))
+    if not os.path.isdir(p):
+        raise AdapterNotFound(f"LoRA adapter directory {path!r} does not exist")
+    cfg_p = os.path.join(p, "adapter_config.json")
+    try:
+        with open(cfg_p, "r", encoding="utf-8") as f:
+            cfg = json.load(f)
+    except (OSError, ValueError) as exc:
+        raise AdapterNotFound(f"cannot read {cfg_p}: {exc}") from exc
+    if not isinstance(cfg, dict) or "r" not in cfg:
+        raise AdapterNotFound(f"{cfg_p}: missing field 'r'")
+    return cfg
 
 
 @runtime_checkable

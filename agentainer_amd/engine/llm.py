@@ -40,6 +40,7 @@ from .kvcache import KVCacheManager, KVCheckpoint, OutOfPages
 from .tokenizer import ByteTokenizer
 from ..models.llama import (AttnMetadata, LLAMA_CONFIGS, LlamaConfig,
                             LlamaForCausalLM)
+from ..models.lora import LoraContext, LoraError, LoraPool, adapter_key
 
 DEFAULT_MAX_NEW = 64
 
@@ -112,6 +113,10 @@ class AgentBinding:
     # whole-page token prefix shared with other agents (system prompt),
     # None when the system prompt is shorter than one KV page
     prefix_tokens: Optional[List[int]] = None
+    # LoRA adapter (canonical directory path) and its pool slot; "" / -1
+    # for a base-model agent
+    adapter: str = ""
+    adapter_slot: int = -1
 
 
 class ModelInstance:
@@ -292,6 +297,24 @@ class ModelInstance:
             self.kvm.dev_seq_lens[self._pad_slot] = -1
             self._pad_slot_t = torch.tensor([self._pad_slot], dtype=torch.long,
                                             device=device)
+        # per-agent LoRA adapters: a fixed pool of adapter slots plus, on
+        # the device-decode path, an int32 mirror (sequence slot -> adapter
+        # slot, -1 = base model / pad row) that the captured decode body
+        # gathers per row, next to kvm.dev_seq_lens. lora_slots == 0: no
+        # pool, no extra graph nodes.
+        self.lora_pool: Optional[LoraPool] = None
+        self.dev_adapter_ids: Optional[torch.Tensor] = None
+        self._seq_adapter: Dict[str, int] = {}  # seq id -> adapter slot
+        lora_slots = int(engine_cfg.get("lora_slots", 0))
+        if (lora_slots > 0 and self.tp_size == 1
+                and isinstance(self.model, LlamaForCausalLM)):
+            self.lora_pool = LoraPool(
+                cfg, lora_slots, int(engine_cfg.get("lora_max_rank", 16)),
+                device)
+            if self.dev_decode:
+                self.dev_adapter_ids = torch.full(
+                    (self.kvm.max_slots,), -1, dtype=torch.int32,
+                    device=device)
 
     @staticmethod
     def _pool_pages(cfg: LlamaConfig, page_size: int, device: str,
@@ -768,7 +791,9 @@ class ModelInstance:
             if (pk is not None and first and is_final and not needs_reset
                     and self.kvm.seq_len(b.seq_id) == 0
                     and len(tokens) > len(pk) and tokens[:len(pk)] == pk):
-                key = tuple(pk)
+                # K/V computed under one adapter is only valid for agents
+                # with that same adapter: its identity is part of the key
+                key = (b.adapter, *pk) if b.adapter else tuple(pk)
                 sid = self._prefixes.get(key)
                 if sid is None:
                     # first user pays: prefill the shared-prefix sequence as
@@ -778,6 +803,8 @@ class ModelInstance:
                     if self.kvm.free_pages >= n_pg + 8:
                         sid = f"\x00pfx:{len(self._prefixes)}"
                         self._prefixes[key] = sid
+                        if b.adapter:  # the payer's adapter computes it
+                            self._seq_adapter[sid] = b.adapter_slot
                         plan.insert(n_extra, (sid, list(pk), False, None))
                         n_extra += 1
                 if sid is not None:
@@ -934,8 +961,22 @@ class ModelInstance:
         last_rows = torch.tensor(
             [s + l - 1 for s, l in zip(q_starts[:n_real], q_lens[:n_real])],
             dtype=torch.long, device=dev)
+        lora = None
+        if self.lora_pool is not None:
+            # prefill knows its segments on the host: one (slot, rows) per
+            # distinct adapter; base-model and pad rows are in no segment
+            seg_rows: Dict[int, List[int]] = {}
+            for sid, start, n in zip(seq_ids, q_starts, q_lens):
+                slot = self._seq_adapter.get(sid, -1)
+                if slot >= 0:
+                    seg_rows.setdefault(slot, []).extend(
+                        range(start, start + n))
+            if seg_rows:
+                lora = LoraContext(self.lora_pool, segments=[
+                    (slot, torch.tensor(rows, dtype=torch.long, device=dev))
+                    for slot, rows in sorted(seg_rows.items())])
         c0 = time.thread_time()
-        out = self.model(input_ids, md, self.kvm.kv_caches(), last_rows)
+        out = self._forward(input_ids, md, last_rows, lora)
         fwd_cpu = (time.thread_time() - c0) * 1000.0
         ema = self._phase_ms.get("pf_fwd_cpu_ms", 0.0)
         self._phase_ms["pf_fwd_cpu_ms"] = 0.05 * fwd_cpu + 0.95 * ema
@@ -943,6 +984,12 @@ class ModelInstance:
         if mn is None or fwd_cpu < mn:
             self._phase_ms["pf_fwd_cpu_min_ms"] = fwd_cpu
         return out
+
+    def _forward(self, input_ids, md, last_rows, lora) -> torch.Tensor:
+        if lora is None:  # exactly the base-model call (any model class)
+            return self.model(input_ids, md, self.kvm.kv_caches(), last_rows)
+        return self.model(input_ids, md, self.kvm.kv_caches(), last_rows,
+                          lora=lora)
 
     # ---------- device-side decode (hipGraph) ----------
 
@@ -959,7 +1006,13 @@ class ModelInstance:
         slots = pages * PS + (pos % PS).long()             # pad rows -> page 0
         md = AttnMetadata(page_table=pt, seq_lens=lens + 1,
                           slot_mapping=slots, positions=pos, is_prefill=False)
-        logits = self.model(input_ids, md, self.kvm.kv_caches(), None)
+        lora = None
+        if self.lora_pool is not None:
+            # which adapter a row uses is device data read inside the
+            # captured body: the batch mix changes without a re-capture
+            lora = LoraContext(self.lora_pool,
+                               ids=self.dev_adapter_ids.index_select(0, rows))
+        logits = self._forward(input_ids, md, None, lora)
         kvm.dev_seq_lens.index_add_(0, rows, inc)
         kvm.dev_seq_lens.index_fill_(0, self._pad_slot_t, -1)
         return logits
@@ -1053,7 +1106,13 @@ class ModelInstance:
             is_prefill=False,
         )
         input_ids = torch.tensor(ids, dtype=torch.long, device=dev)
-        return self.model(input_ids, md, self.kvm.kv_caches(), None)
+        lora = None
+        if self.lora_pool is not None:
+            a_ids = [self._seq_adapter.get(sid, -1) for sid in seq_ids]
+            if any(a >= 0 for a in a_ids):
+                lora = LoraContext(self.lora_pool, ids=torch.tensor(
+                    a_ids, dtype=torch.int32, device=dev))
+        return self._forward(input_ids, md, None, lora)
 
     def _decode_exec_gpu(self, plan) -> torch.Tensor:
         kvm = self.kvm
@@ -1226,10 +1285,23 @@ class ModelInstance:
     def _bind_locked(self, agent, seq_id: str, ckpt: Optional[KVCheckpoint],
                      worker_has_ckpt: bool = False):
         with self._lock:
-            self._bcast(("bind", self.name, seq_id,
-                         ckpt is not None or worker_has_ckpt))
-            self._bind_seq(seq_id, ckpt)
-            b = AgentBinding(agent=agent, model_name=self.name, seq_id=seq_id)
+            adapter, a_slot = self._acquire_adapter(agent), -1
+            if adapter:
+                a_slot = self.lora_pool.acquire(adapter)
+            try:
+                self._bcast(("bind", self.name, seq_id,
+                             ckpt is not None or worker_has_ckpt))
+                self._bind_seq(seq_id, ckpt)
+            except Exception:
+                if adapter:
+                    self.lora_pool.release(adapter)
+                raise
+            b = AgentBinding(agent=agent, model_name=self.name, seq_id=seq_id,
+                             adapter=adapter, adapter_slot=a_slot)
+            if adapter:
+                self._seq_adapter[seq_id] = a_slot
+                if self.dev_adapter_ids is not None:
+                    self.dev_adapter_ids[self.kvm.slot(seq_id)] = a_slot
             sp = getattr(agent, "system_prompt", "") or ""
             if self.prefix_sharing and sp:
                 # the whole-page head of this agent's first-turn prompt
@@ -1240,6 +1312,28 @@ class ModelInstance:
                     b.prefix_tokens = pk[:n_full]
             self._bindings[agent.id] = b
             self.refcount += 1
+
+    def _acquire_adapter(self, agent) -> str:
+        """Canonical path of the agent's LoRA adapter ("" = base model).
+        A configuration that cannot serve the adapter is an error: an agent
+        that names one is never silently served by the base model."""
+        path = getattr(agent, "lora", "") or ""
+        if not path:
+            return ""
+        if self.tp_size > 1:
+            raise LoraError(
+                f"agent {agent.id}: LoRA adapters are not supported with "
+                f"tp_degree={self.tp_size} (tensor-parallel LoRA is not "
+                "implemented)")
+        if not isinstance(self.model, LlamaForCausalLM):
+            raise LoraError(
+                f"agent {agent.id}: LoRA adapters are not supported on "
+                f"model {self.name!r} (Llama-family dense models only)")
+        if self.lora_pool is None:
+            raise LoraError(
+                f"agent {agent.id} names LoRA adapter {path!r} but LoRA is "
+                "disabled: set engine.lora_slots > 0 to enable it")
+        return adapter_key(path)
 
     def unbind(self, agent_id: str, offload: bool) -> Optional[KVCheckpoint]:
         locked = True
@@ -1282,6 +1376,11 @@ class ModelInstance:
                     break
                 r.error = "agent detached"
                 r.done.set()
+        if b.adapter:
+            self._seq_adapter.pop(b.seq_id, None)
+            if self.dev_adapter_ids is not None and self.kvm.has_seq(b.seq_id):
+                self.dev_adapter_ids[self.kvm.slot(b.seq_id)] = -1
+            self.lora_pool.release(b.adapter)
         self._bcast(("unbind", self.name, b.seq_id, offload))
         ckpt = self.kvm.offload(b.seq_id, free=True) if offload else None
         if not offload:
@@ -1369,6 +1468,9 @@ class LLMEngine:
         model = agent.model
         from .echo import ECHO_MODELS
         if model in ECHO_MODELS:
+            if getattr(agent, "lora", ""):
+                raise LoraError(f"agent {agent.id}: the echo model takes no "
+                                "LoRA adapter")
             # echo agents need no weights; emulate with tiny state
             with self._lock:
                 self._agent_model[agent.id] = "echo"
@@ -1727,6 +1829,10 @@ class LLMEngine:
                 "kv_pages_free": inst.kvm.free_pages,
                 "kv_pages_shared": len(inst.kvm._refs),
                 "shared_prefixes": len(inst._prefixes),
+                "lora": ({"slots": inst.lora_pool.slots,
+                          "max_rank": inst.lora_pool.max_rank,
+                          "resident": inst.lora_pool.resident()}
+                         if inst.lora_pool is not None else None),
                 "kv_dtype": str(inst.kvm.dtype).replace("torch.", ""),
                 "running": len(inst.running),
                 "stuck": inst.stuck(),

@@ -97,10 +97,14 @@ class LlamaAttention(torch.nn.Module):
         self.o_q = None
 
     def forward(self, h, k_cache, v_cache, md: AttnMetadata, cos_sin,
-                tp_group=None, defer_reduce: bool = False):
+                tp_group=None, defer_reduce: bool = False, lora=None,
+                layer_idx: int = 0):
         """defer_reduce: the caller feeds the result straight into
         ops.fused_add_rmsnorm, so a split-K o-proj may come back as an
-        ops.SplitKPartial (never under TP: the all-reduce needs bf16)."""
+        ops.SplitKPartial (never under TP: the all-reduce needs bf16, and
+        never with a LoRA pool attached: the delta is added to bf16 too).
+        lora: models.lora.LoraContext or None; each projection's adapter
+        delta is added to its GEMM output in place."""
         T = h.size(0)
         if self.qkv_q is not None and T <= 64 and h.is_cuda:
             qkv = ops.linear_quant(h, self.qkv_q)
@@ -108,6 +112,8 @@ class LlamaAttention(torch.nn.Module):
             qkv = ops.linear(h, self.qkv_proj, self.qkv_packed)
         if self.qkv_bias is not None:
             qkv = qkv + self.qkv_bias
+        if lora is not None:
+            lora.apply(layer_idx, "qkv", qkv, h)
         q_sz = self.n_heads * self.head_dim
         kv_sz = self.n_kv * self.head_dim
         # strided views into the fused GEMM output — the HIP kernels take
@@ -129,11 +135,13 @@ class LlamaAttention(torch.nn.Module):
                                        md.seq_lens, self.scale)
         if self.o_q is not None and T <= 64 and h.is_cuda:
             o = ops.linear_quant(out.view(T, q_sz), self.o_q)
-        elif defer_reduce and tp_group is None:
+        elif defer_reduce and tp_group is None and lora is None:
             o = ops.linear_partial(out.view(T, q_sz), self.o_proj,
                                    self.o_packed)
         else:
             o = ops.linear(out.view(T, q_sz), self.o_proj, self.o_packed)
+        if lora is not None:
+            lora.apply(layer_idx, "o", o, out.view(T, q_sz))
         if tp_group is not None:
             torch.distributed.all_reduce(o, group=tp_group)
         return o
@@ -153,23 +161,28 @@ class LlamaMLP(torch.nn.Module):
         self.gate_up_q = None
         self.down_q = None
 
-    def forward(self, h, tp_group=None, defer_reduce: bool = False):
-        # defer_reduce: as in LlamaAttention.forward, for the down-proj
+    def forward(self, h, tp_group=None, defer_reduce: bool = False,
+                lora=None, layer_idx: int = 0):
+        # defer_reduce, lora: as in LlamaAttention.forward, for the down-proj
         turbo = self.gate_up_q is not None and h.size(0) <= 64 and h.is_cuda
         if turbo:
             gu = ops.linear_quant(h, self.gate_up_q)
         else:
             gu = ops.linear(h, self.gate_up, self.gate_up_packed)
+        if lora is not None:
+            lora.apply(layer_idx, "gate_up", gu, h)
         gate, up = gu[:, :self.inter], gu[:, self.inter:]
         act = torch.empty(gu.size(0), self.inter, dtype=gu.dtype,
                           device=gu.device)
         ops.silu_mul(act, gate, up)
         if turbo:
             out = ops.linear_quant(act, self.down_q)
-        elif defer_reduce and tp_group is None:
+        elif defer_reduce and tp_group is None and lora is None:
             out = ops.linear_partial(act, self.down, self.down_packed)
         else:
             out = ops.linear(act, self.down, self.down_packed)
+        if lora is not None:
+            lora.apply(layer_idx, "down", out, act)
         if tp_group is not None:
             torch.distributed.all_reduce(out, group=tp_group)
         return out
@@ -185,7 +198,8 @@ class LlamaLayer(torch.nn.Module):
         self.eps = cfg.norm_eps
 
     def forward(self, hidden, residual, k_cache, v_cache, md, cos_sin,
-                tp_group=None, defer_reduce: bool = False):
+                tp_group=None, defer_reduce: bool = False, lora=None,
+                layer_idx: int = 0):
         """hidden may be the previous layer's ops.SplitKPartial; with
         defer_reduce the returned mlp_out may be one too (the caller's next
         fused_add_rmsnorm reduces it)."""
@@ -197,10 +211,11 @@ class LlamaLayer(torch.nn.Module):
             normed = torch.empty_like(residual)
             ops.fused_add_rmsnorm(normed, hidden, residual, self.input_ln, self.eps)
         attn_out = self.attn(normed, k_cache, v_cache, md, cos_sin, tp_group,
-                             defer_reduce=True)
+                             defer_reduce=True, lora=lora, layer_idx=layer_idx)
         normed2 = torch.empty_like(residual)
         ops.fused_add_rmsnorm(normed2, attn_out, residual, self.post_ln, self.eps)
-        mlp_out = self.mlp(normed2, tp_group, defer_reduce=defer_reduce)
+        mlp_out = self.mlp(normed2, tp_group, defer_reduce=defer_reduce,
+                           lora=lora, layer_idx=layer_idx)
         return mlp_out, residual
 
 
@@ -245,16 +260,19 @@ class LlamaForCausalLM(torch.nn.Module):
 
     @torch.no_grad()
     def forward(self, input_ids: torch.Tensor, md: AttnMetadata,
-                kv_caches: List, last_rows: Optional[torch.Tensor] = None
-                ) -> torch.Tensor:
-        """Returns logits for `last_rows` (defaults: all rows)."""
+                kv_caches: List, last_rows: Optional[torch.Tensor] = None,
+                lora=None) -> torch.Tensor:
+        """Returns logits for `last_rows` (defaults: all rows). lora: an
+        optional models.lora.LoraContext (adapter pool + per-row slot ids
+        or prefill segments); None is exactly the base-model path."""
         hidden = F.embedding(input_ids, self.embed)
         residual = None
         for i, layer in enumerate(self.layers):
             k_cache, v_cache = kv_caches[i]
             hidden, residual = layer(hidden, residual, k_cache, v_cache, md,
                                      self.cos_sin, self.tp_group,
-                                     defer_reduce=True)
+                                     defer_reduce=True, lora=lora,
+                                     layer_idx=i)
         final = torch.empty_like(residual)
         ops.fused_add_rmsnorm(final, hidden, residual, self.final_ln, self.cfg.norm_eps)
         if last_rows is not None:

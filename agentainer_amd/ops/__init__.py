@@ -438,6 +438,56 @@ def linear_quant(x: torch.Tensor, qt) -> torch.Tensor:
     return linear_fp8(x, packed, scales, N)
 
 
+def lora_shrink(v, x, A, ids):
+    """v[t, :] = A[ids[t]] @ x[t] (f32 [T, R]); rows with ids[t] < 0 get
+    zeros. x bf16 [T, K] (row-strided), A bf16 [S, R, K], ids int32 [T]."""
+    mod = _dispatch("lora_shrink", x)
+    if mod:
+        mod.lora_shrink(v, x, A, ids)
+    else:
+        reference.lora_shrink(v, x, A, ids)
+    return v
+
+
+def lora_expand_add(y, v, B, ids):
+    """y[t, :] += B[ids[t]] @ v[t] in place (y bf16 [T, N], row-strided;
+    B bf16 [S, N, R]); rows with ids[t] < 0 are left untouched."""
+    mod = _dispatch("lora_expand_add", y)
+    if mod:
+        mod.lora_expand_add(y, v, B, ids)
+    else:
+        reference.lora_expand_add(y, v, B, ids)
+    return y
+
+
+_lora_ws_cache = {}
+
+
+def _lora_ws(device, n: int) -> torch.Tensor:
+    # keyed like _skinny_ws_slot: a side-stream prefill must not write the
+    # rank-space buffer a decode graph on another stream is still reading
+    stream = (torch.cuda.current_stream(device).cuda_stream
+              if device.type == "cuda" else 0)
+    key = (device, stream)
+    ws = _lora_ws_cache.get(key)
+    if ws is None or ws.numel() < n:
+        ws = torch.empty(n, dtype=torch.float32, device=device)
+        _lora_ws_cache[key] = ws
+    return ws
+
+
+def lora_apply(y, x, A, B, ids):
+    """y += B[ids] @ (A[ids] @ x) per row: shrink into a cached f32
+    workspace, then expand-add into y in place."""
+    T, R = x.size(0), A.size(1)
+    if T == 0:
+        return y
+    v = _lora_ws(x.device, T * R)[:T * R].view(T, R)
+    lora_shrink(v, x, A, ids)
+    lora_expand_add(y, v, B, ids)
+    return y
+
+
 def gather_kv_pages(dst, k_cache, v_cache, page_ids):
     mod = _dispatch("gather_kv_pages", k_cache)
     if mod:

@@ -41,6 +41,7 @@ SOURCES = [
     "prefill_attn.hip",
     "sampling.hip",
     "skinny_gemm.hip",
+    "lora.hip",
 ]
 
 

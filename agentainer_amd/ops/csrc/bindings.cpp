@@ -47,6 +47,10 @@ void skinny_gemm_fp8(torch::Tensor out, torch::Tensor x8, torch::Tensor sx,
 void mfma_probe(torch::Tensor c, torch::Tensor a, torch::Tensor b);
 void scatter_kv_pages(torch::Tensor k_cache, torch::Tensor v_cache,
                       torch::Tensor src, torch::Tensor page_ids);
+void lora_shrink(torch::Tensor v, torch::Tensor x, torch::Tensor A,
+                 torch::Tensor ids);
+void lora_expand_add(torch::Tensor y, torch::Tensor v, torch::Tensor B,
+                     torch::Tensor ids);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "agentainer_amd CDNA4 (gfx950) kernels";
@@ -79,4 +83,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_fp8", &skinny_gemm_fp8, "fp8 MFMA skinny GEMM");
   m.def("mfma_probe", &mfma_probe, "single 16x16x32 bf16 MFMA on prepacked fragments");
   m.def("scatter_kv_pages", &scatter_kv_pages, "buffer -> pages");
+  m.def("lora_shrink", &lora_shrink,
+        "v[t] = A[ids[t]] @ x[t] (f32), zeros where ids[t] < 0");
+  m.def("lora_expand_add", &lora_expand_add,
+        "y[t] += B[ids[t]] @ v[t] in place, rows with ids[t] < 0 untouched");
 }

@@ -180,3 +180,25 @@ def scatter_kv_pages(k_cache: torch.Tensor, v_cache: torch.Tensor,
     for i, p in enumerate(page_ids.tolist()):
         k_cache[p] = flat[i * 2 * plane:(i * 2 + 1) * plane].view_as(k_cache[p])
         v_cache[p] = flat[(i * 2 + 1) * plane:(i + 1) * 2 * plane].view_as(v_cache[p])
+
+
+def lora_shrink(v: torch.Tensor, x: torch.Tensor, A: torch.Tensor,
+                ids: torch.Tensor) -> None:
+    """v[t] = A[ids[t]] @ x[t] in f32; rows with ids[t] < 0 get zeros and
+    never index A."""
+    v.zero_()
+    live = (ids >= 0).nonzero().squeeze(1)
+    if live.numel():
+        a = A[ids[live].long()].float()                    # [n, R, K]
+        v[live] = torch.einsum("nrk,nk->nr", a, x[live].float())
+
+
+def lora_expand_add(y: torch.Tensor, v: torch.Tensor, B: torch.Tensor,
+                    ids: torch.Tensor) -> None:
+    """y[t] = bf16(f32(y[t]) + B[ids[t]] @ v[t]) in place; rows with
+    ids[t] < 0 are not touched."""
+    live = (ids >= 0).nonzero().squeeze(1)
+    if live.numel():
+        b = B[ids[live].long()].float()                    # [n, N, R]
+        d = torch.einsum("nor,nr->no", b, v[live].float())
+        y[live] = (y[live].float() + d).to(y.dtype)

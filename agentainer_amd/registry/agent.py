@@ -66,6 +66,7 @@ class Agent:
     token: Optional[str] = None      # per-agent token — honored (ref stores but ignores it)
     health_check: Optional[Dict[str, Any]] = None
     system_prompt: str = ""
+    lora: str = ""                   # LoRA adapter directory; "" = base model
     sampling: Dict[str, Any] = field(default_factory=dict)
     created_at: float = 0.0
     updated_at: float = 0.0
@@ -148,18 +149,25 @@ class Manager:
         health_check: Optional[Dict[str, Any]] = None,
         system_prompt: str = "",
         sampling: Optional[Dict[str, Any]] = None,
+        lora: str = "",
     ) -> Agent:
         """Register an agent. Validates the model exists (analog of the
-        image-must-exist check, agent.go:106-112) but allocates nothing."""
+        image-must-exist check, agent.go:106-112) and, when a LoRA adapter
+        is named, that its directory and adapter_config.json are readable
+        — but allocates nothing."""
         with self._lock:
             self.engine.validate_model(model)
+            lora = str(lora or "")
+            if lora:
+                from ..engine.base import validate_adapter_dir
+                validate_adapter_dir(lora)
             agent = Agent(
                 id=f"agent-{uuid.uuid4().hex[:12]}",
                 name=name, model=model, dtype=dtype, tp_degree=tp_degree,
                 kv_budget=kv_budget, max_context=max_context,
                 env=dict(env or {}), auto_restart=auto_restart, token=token,
                 health_check=health_check, system_prompt=system_prompt,
-                sampling=dict(sampling or {}),
+                lora=lora, sampling=dict(sampling or {}),
                 created_at=time.time(),
             )
             self._save(agent)
