@@ -178,21 +178,26 @@ SKINNY_FORCED = os.environ.get("AGENTAINER_FORCE_SKINNY", "0") == "1"
 # A/B hook: linear_partial always combines (no deferred split-K reduction)
 SPLITK_DEFER_DISABLED = (
     os.environ.get("AGENTAINER_DISABLE_SPLITK_DEFER", "0") == "1")
-# shapes where the hand-written skinny GEMM beat hipBLASLt on MI355X,
-# with the (split_k, k_chunk) that won the tools/sg_sweep.py grid
-# (M=64; see profiles/README.md). Library keeps qkv/gate_up: at
-# N>=6144 its MT256 tiles already stream near the roofline.
+# shapes where the hand-written skinny GEMM beat hipBLASLt on MI355X, as
+# (split_k, k_chunk, tiles per wave), decided by in-graph kernel averages
+# (profiles/README.md, "Wide-tile skinny GEMM"). The library keeps qkv
+# (19.2 us vs 20.6 best skinny, cold) and gate_up (48-50 us vs 53-57; a
+# SwiGLU epilogue did not make up the difference: 59.3 vs 52.0 + 4.9).
 _SKINNY_SHAPES = {
-    (4096, 4096): (4, 128),    # o-proj: 14.2 us vs lib 18.6
-    (4096, 14336): (8, 128),   # down-proj: 30.3 us vs lib 34.4
+    # o-proj 14.5 us in-graph. nw=2 loses at split 4 (19.4 vs 17.4 cold);
+    # (8, 128, 2) runs 12.0 us but would change the accumulation order
+    (4096, 4096): (4, 128, 1),
+    # down-proj: nw 1 -> 2 took it from 36.1-36.8 to 30.5-31.6 us in-graph,
+    # bit-identical (same split and k_chunk)
+    (4096, 14336): (8, 128, 2),
 }
 SKINNY_NT = os.environ.get("AGENTAINER_SKINNY_NT", "0") == "1"
 SKINNY_KC = int(os.environ.get("AGENTAINER_SKINNY_KC", "0"))  # 0 = tuned
-# A/B hook: extra tuned shapes as "N:K:split:kc,..." (perf experiments)
+# A/B hook: extra tuned shapes as "N:K:split:kc[:nw],..." (perf experiments)
 for _spec in os.environ.get("AGENTAINER_SKINNY_SHAPES", "").split(","):
     if _spec.strip():
-        _n, _k, _s, _c = (int(v) for v in _spec.split(":"))
-        _SKINNY_SHAPES[(_n, _k)] = (_s, _c)
+        _n, _k, _s, _c, *_w = (int(v) for v in _spec.split(":"))
+        _SKINNY_SHAPES[(_n, _k)] = (_s, _c, _w[0] if _w else 1)
 
 
 def _skinny_split(ntiles: int, K: int) -> int:
@@ -293,7 +298,7 @@ def _linear(x, w, w_packed, defer: bool):
     if (x.is_cuda and M <= 64 and N % 64 == 0 and K % 256 == 0
             and (tuned is not None or SKINNY_FORCED) and not SKINNY_DISABLED):
         mod = _dispatch("skinny_gemm", x)
-        split, kc = tuned if tuned else (_skinny_split(N // 64, K), 128)
+        split, kc, nw = tuned if tuned else (_skinny_split(N // 64, K), 128, 1)
         if SKINNY_KC:
             kc = SKINNY_KC
         if K % (kc * split):
@@ -308,7 +313,7 @@ def _linear(x, w, w_packed, defer: bool):
             out = torch.empty(M, N, dtype=x.dtype, device=x.device)
         if w_packed is not None:
             mod.skinny_gemm_packed(out, x.contiguous(), w_packed, N, K, ws,
-                                   split, SKINNY_NT, kc, not defer)
+                                   split, SKINNY_NT, kc, not defer, nw)
         else:
             mod.skinny_gemm(out, x.contiguous(), w, ws, split, not defer)
         return SplitKPartial(slot, split, M, N) if defer else out

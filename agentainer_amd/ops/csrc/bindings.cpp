@@ -32,7 +32,7 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
                         torch::Tensor w_packed, long N, long K,
                         torch::Tensor ws, long split, bool nt, long kc,
-                        bool combine);
+                        bool combine, long nw);
 void splitk_add_rmsnorm(torch::Tensor out, torch::Tensor ws, long split,
                         long M, long N, torch::Tensor residual,
                         torch::Tensor w, double eps);
@@ -76,7 +76,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_gemm_packed", &skinny_gemm_packed, "packed-weight skinny GEMM",
         py::arg("out"), py::arg("x"), py::arg("w_packed"), py::arg("N"),
         py::arg("K"), py::arg("ws"), py::arg("split"), py::arg("nt"),
-        py::arg("kc"), py::arg("combine") = true);
+        py::arg("kc"), py::arg("combine") = true, py::arg("nw") = 1);
   m.def("skinny_gemm_mxfp4", &skinny_gemm_mxfp4, "MXFP4 block-scaled expert GEMM");
   m.def("quant_fp4_rows", &quant_fp4_rows, "per-row e2m1 activation quant");
   m.def("quant_fp8_rows", &quant_fp8_rows, "per-row bf16 -> e4m3 quant");

@@ -213,12 +213,18 @@ void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
 
 namespace {
 
-template <bool SPLIT, bool FULL, bool NT, int KC>
+// NW: 16-col tiles per wave. A block covers 64*NW columns; wave w owns
+// tiles (blockIdx.x*4 + w)*NW + t. Each x fragment read from LDS feeds NW
+// MFMAs, and NW weight streams are in flight per wave across each barrier,
+// so x re-staging, LDS reads and barriers per W byte all drop by NW. Every
+// output element still accumulates the same products in the same order,
+// so results are bit-identical across NW for a given (split, KC).
+template <bool SPLIT, bool FULL, bool NT, int KC, int NW>
 __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
     void* __restrict__ out, const short* __restrict__ x,
     const short* __restrict__ wp_packed, int M, int N, int K,
     int k_per_split) {
-  const int n_tile = blockIdx.x * 4 + threadIdx.x / WAVE;  // 16-col tile
+  const int n_tile = (blockIdx.x * 4 + threadIdx.x / WAVE) * NW;  // first tile
   const int split = blockIdx.y;
   const int lane = threadIdx.x % WAVE;
   const int l16 = lane % 16;
@@ -226,11 +232,14 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   const int k0 = split * k_per_split;
   const int k1 = min(k0 + k_per_split, K);
 
-  f32x4 acc[4];
+  f32x4 acc[NW][4];
 #pragma unroll
-  for (int ms = 0; ms < 4; ++ms) acc[ms] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < NW; ++t)
+#pragma unroll
+    for (int ms = 0; ms < 4; ++ms) acc[t][ms] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  // this wave's contiguous weight stream
+  // this wave's NW contiguous weight streams, one tile_stride apart
+  const long tile_stride = (long)(K / 32) * 512;
   const short* wp = wp_packed + ((long)n_tile * (K / 32) + k0 / 32) * 512 +
                     lane * 8;
 
@@ -265,16 +274,21 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   // t+1's eight nt loads are issued while chunk t computes, so no chunk
   // pays the ~900-cycle HBM latency cold (the barrier would otherwise
   // serialize it at 1-2 blocks/CU).
-  bf16v8 bw_cur[FR], bw_nxt[FR];
-  auto w_load = [&](bf16v8 (&dst)[FR], long woff) {
+  bf16v8 bw_cur[NW][FR], bw_nxt[NW][FR];
+  auto w_load = [&](bf16v8 (&dst)[NW][FR], long woff) {
 #pragma unroll
-    for (int i = 0; i < FR; ++i) {
-      const bf16v8* p = reinterpret_cast<const bf16v8*>(wp + woff + (long)i * 512);
-      dst[i] = NT ? __builtin_nontemporal_load(p) : *p;
+    for (int t = 0; t < NW; ++t) {
+#pragma unroll
+      for (int i = 0; i < FR; ++i) {
+        const bf16v8* p = reinterpret_cast<const bf16v8*>(
+            wp + t * tile_stride + woff + (long)i * 512);
+        dst[t][i] = NT ? __builtin_nontemporal_load(p) : *p;
+      }
     }
   };
 
-  auto compute = [&](bf16v8 (&bw)[FR], int buf) {
+  // each a[ms] fragment is read from LDS once per k-step and feeds NW MFMAs
+  auto compute = [&](bf16v8 (&bw)[NW][FR], int buf) {
 #pragma unroll
     for (int i = 0; i < FR; ++i) {
       bf16v8 a[4];
@@ -283,9 +297,11 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
         a[ms] = *reinterpret_cast<const bf16v8*>(
             &x_lds[buf][(ms * 16 + l16) * XS + i * 32 + lg * 8]);
 #pragma unroll
-      for (int ms = 0; ms < 4; ++ms)
-        acc[ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ms], bw[i],
-                                                          acc[ms], 0, 0, 0);
+      for (int t = 0; t < NW; ++t)
+#pragma unroll
+        for (int ms = 0; ms < 4; ++ms)
+          acc[t][ms] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a[ms], bw[t][i], acc[t][ms], 0, 0, 0);
     }
   };
   stage_load(k0);
@@ -326,21 +342,62 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
   }
 
 #pragma unroll
-  for (int ms = 0; ms < 4; ++ms) {
+  for (int t = 0; t < NW; ++t) {
+    const int col = (n_tile + t) * 16 + l16;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = ms * 16 + lg * 4 + r;
-      if (row >= M) continue;
-      const int col = n_tile * 16 + l16;
-      if (SPLIT) {
-        float* o = reinterpret_cast<float*>(out);
-        o[((long)split * M + row) * N + col] = acc[ms][r];
-      } else {
-        short* o = reinterpret_cast<short*>(out);
-        o[(long)row * N + col] = f2bits(acc[ms][r]);
+    for (int ms = 0; ms < 4; ++ms) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = ms * 16 + lg * 4 + r;
+        if (row >= M) continue;
+        if (SPLIT) {
+          float* o = reinterpret_cast<float*>(out);
+          o[((long)split * M + row) * N + col] = acc[t][ms][r];
+        } else {
+          short* o = reinterpret_cast<short*>(out);
+          o[(long)row * N + col] = f2bits(acc[t][ms][r]);
+        }
       }
     }
   }
+}
+
+struct SgpArgs {
+  void* out;
+  const short* x;
+  const short* w;
+  int M, N, K, kps, split;
+  bool full, nt;
+  hipStream_t stream;
+};
+
+template <bool SPLIT, int KC, int NW>
+void sgp_launch(const SgpArgs& a) {
+  const dim3 grid(a.N / (64 * NW), SPLIT ? a.split : 1);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, a.stream, a.out, a.x, a.w,
+                       a.M, a.N, a.K, a.kps);
+  };
+  if (a.full && a.nt)
+    go(skinny_gemm_packed_kernel<SPLIT, true, true, KC, NW>);
+  else if (a.full)
+    go(skinny_gemm_packed_kernel<SPLIT, true, false, KC, NW>);
+  else if (a.nt)
+    go(skinny_gemm_packed_kernel<SPLIT, false, true, KC, NW>);
+  else
+    go(skinny_gemm_packed_kernel<SPLIT, false, false, KC, NW>);
+}
+
+template <bool SPLIT>
+void sgp_dispatch(const SgpArgs& a, long kc, long nw) {
+  if (kc == 128) {
+    if (nw == 4) return sgp_launch<SPLIT, 128, 4>(a);
+    if (nw == 2) return sgp_launch<SPLIT, 128, 2>(a);
+    return sgp_launch<SPLIT, 128, 1>(a);
+  }
+  if (nw == 4) return sgp_launch<SPLIT, 256, 4>(a);
+  if (nw == 2) return sgp_launch<SPLIT, 256, 2>(a);
+  return sgp_launch<SPLIT, 256, 1>(a);
 }
 
 }  // namespace
@@ -348,7 +405,7 @@ __global__ __launch_bounds__(256) void skinny_gemm_packed_kernel(
 void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
                         torch::Tensor w_packed, long N, long K,
                         torch::Tensor ws, long split, bool nt, long kc,
-                        bool combine) {
+                        bool combine, long nw) {
   TORCH_CHECK(x.is_contiguous() && w_packed.is_contiguous() && out.is_contiguous());
   TORCH_CHECK(x.scalar_type() == at::kBFloat16 &&
               w_packed.scalar_type() == at::kBFloat16);
@@ -357,47 +414,32 @@ void skinny_gemm_packed(torch::Tensor out, torch::Tensor x,
   TORCH_CHECK(w_packed.numel() == N * K, "packed weight numel mismatch");
   TORCH_CHECK(M <= 64 && N % 64 == 0 && K % 256 == 0);
   TORCH_CHECK(split >= 1 && (K % (256 * split)) == 0);
-  auto stream = at::hip::getCurrentHIPStream();
-  const int ntiles = (int)N / 64;
-  const int kps = (int)K / (int)split;
-  const bool full = (M == 64);
+  TORCH_CHECK(nw == 1 || nw == 2 || nw == 4, "nw must be 1, 2 or 4");
+  TORCH_CHECK(N % (64 * nw) == 0, "skinny_gemm_packed: N % (64*nw) == 0");
   TORCH_CHECK(kc == 128 || kc == 256, "kc must be 128 or 256");
   TORCH_CHECK((K % (kc * split)) == 0, "K must be kc*split aligned");
-#define SGP_LAUNCH(SPLIT_, FULL_, NT_, KC_, OUTP)                              \
-  hipLaunchKernelGGL((skinny_gemm_packed_kernel<SPLIT_, FULL_, NT_, KC_>),     \
-                     dim3(ntiles, SPLIT_ ? (int)split : 1), dim3(256), 0,      \
-                     stream, OUTP, (const short*)x.data_ptr(),                 \
-                     (const short*)w_packed.data_ptr(), M, (int)N, (int)K, kps)
-#define SGP_KC(SPLIT_, FULL_, NT_, OUTP)                                       \
-  do {                                                                         \
-    if (kc == 128) SGP_LAUNCH(SPLIT_, FULL_, NT_, 128, OUTP);                  \
-    else SGP_LAUNCH(SPLIT_, FULL_, NT_, 256, OUTP);                            \
-  } while (0)
-#define SGP_DISPATCH(SPLIT_, OUTP)                                             \
-  do {                                                                         \
-    if (full && nt) SGP_KC(SPLIT_, true, true, OUTP);                          \
-    else if (full) SGP_KC(SPLIT_, true, false, OUTP);                          \
-    else if (nt) SGP_KC(SPLIT_, false, true, OUTP);                            \
-    else SGP_KC(SPLIT_, false, false, OUTP);                                   \
-  } while (0)
+  SgpArgs a{nullptr, (const short*)x.data_ptr(),
+            (const short*)w_packed.data_ptr(), M, (int)N, (int)K,
+            (int)K / (int)split, (int)split, M == 64, nt,
+            at::hip::getCurrentHIPStream()};
   if (split == 1) {
     TORCH_CHECK(out.numel() >= (long)M * N,
                 "skinny_gemm_packed: out smaller than [M,N]");
-    SGP_DISPATCH(false, out.data_ptr());
+    a.out = out.data_ptr();
+    sgp_dispatch<false>(a, kc, nw);
   } else {
     TORCH_CHECK(ws.numel() >= (long)split * M * N && ws.scalar_type() == at::kFloat);
-    SGP_DISPATCH(true, ws.data_ptr());
+    a.out = ws.data_ptr();
+    sgp_dispatch<true>(a, kc, nw);
     if (combine) {
       const long mn = (long)M * N;
       TORCH_CHECK(out.numel() >= mn,
                   "skinny_gemm_packed: out smaller than [M,N]");
       hipLaunchKernelGGL(splitk_combine_kernel, dim3((mn + 1023) / 1024),
-                         dim3(256), 0, stream, (short*)out.data_ptr(),
+                         dim3(256), 0, a.stream, (short*)out.data_ptr(),
                          ws.data_ptr<float>(), mn, split);
     }
   }
-#undef SGP_DISPATCH
-#undef SGP_LAUNCH
 }
 
 // ---------------------------------------------------------------------------
