@@ -215,12 +215,26 @@ def logs(client: Client, agent_id: str, limit: int, follow: bool):
 @click.argument("agent_id")
 @click.option("--message", "-m", required=True)
 @click.option("--stream", is_flag=True, help="stream tokens as they decode (SSE)")
+@click.option("--sampling", default="",
+              help="per-request sampling overrides as JSON, e.g. "
+                   '\'{"top_k": 40, "repetition_penalty": 1.1}\'')
 @pass_client
-def invoke(client: Client, agent_id: str, message: str, stream: bool):
+def invoke(client: Client, agent_id: str, message: str, stream: bool,
+           sampling: str):
     """Send a chat message to an agent (authenticated dispatch)."""
+    body = {"message": message}
+    if sampling:
+        try:
+            body["sampling"] = json.loads(sampling)
+        except ValueError as exc:
+            click.echo(f"error: --sampling is not valid JSON: {exc}", err=True)
+            sys.exit(2)
+        if not isinstance(body["sampling"], dict):
+            click.echo("error: --sampling must be a JSON object", err=True)
+            sys.exit(2)
     if stream:
         with httpx.stream("POST", f"{client.url}/agent/{agent_id}/chat",
-                          json={"message": message, "stream": True},
+                          json={**body, "stream": True},
                           timeout=120.0) as r:
             if r.status_code != 200:
                 click.echo(f"error ({r.status_code})", err=True)
@@ -237,8 +251,7 @@ def invoke(client: Client, agent_id: str, message: str, stream: bool):
                     click.echo(ev.get("text", ""), nl=False)
         return
     resp = client.call("POST", f"/agents/{agent_id}/invoke",
-                       {"path": "/chat", "method": "POST",
-                        "body": {"message": message}})
+                       {"path": "/chat", "method": "POST", "body": body})
     data = resp.get("data")
     if isinstance(data, dict) and "response" in data:
         click.echo(data["response"])

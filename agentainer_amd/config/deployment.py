@@ -60,7 +60,10 @@ class AgentSpec:
     health_check: Optional[Dict[str, Any]] = None
     system_prompt: str = ""
     lora: str = ""               # LoRA adapter directory; "" = base model
-    sampling: Dict[str, Any] = field(default_factory=dict)  # temperature/top_p/top_k/max_tokens
+    # temperature/top_p/seed/max_tokens, and the extended controls top_k/
+    # min_p/repetition_penalty/presence_penalty/frequency_penalty/logit_bias
+    # (defaults here, overridable per request; docs/API_ENDPOINTS.md)
+    sampling: Dict[str, Any] = field(default_factory=dict)
     dependencies: List[str] = field(default_factory=list)
 
     def to_dict(self) -> Dict[str, Any]:

@@ -22,6 +22,11 @@ class AdapterNotFound(ModelNotFound):
     """Deploy named a LoRA adapter directory that is missing or unreadable."""
 
 
+class InvalidSampling(ValueError):
+    """A request's `sampling` values are ill-typed or out of range: the
+    client's error, so the request fails instead of waiting for a replay."""
+
+
 def validate_adapter_dir(path: str) -> Dict[str, Any]:
     """Deploy-time check of an agent's `lora` field: the directory exists
     and its adapter_config.json parses. Returns the parsed config. Shapes

@@ -28,14 +28,14 @@ import threading
 import time
 import traceback
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, List, Optional, Tuple
 
 import torch
 
 from .. import ops
 from .. import parallel as par
 from ..store import Store
-from .base import ModelNotFound
+from .base import InvalidSampling, ModelNotFound
 from .kvcache import KVCacheManager, KVCheckpoint, OutOfPages
 from .tokenizer import ByteTokenizer
 from ..models.llama import (AttnMetadata, LLAMA_CONFIGS, LlamaConfig,
@@ -54,7 +54,9 @@ OP_BARRIER = 2  # [OP] — timing fence (bench.py --tp)
 # device sample (logits are bitwise-identical across ranks after the
 # all-reduce, and sampling is seed-deterministic, so every rank samples
 # the same token without any extra communication)
-OP_DECODE_ASYNC = 3  # [OP, model_idx, B, nrb, rb_slot*nrb, row*6*B]
+# When a row uses the extended sampling controls a tail follows the 6*B
+# block (ModelInstance._send_ext_tail); without one the vector is unchanged.
+OP_DECODE_ASYNC = 3  # [OP, model_idx, B, nrb, rb_slot*nrb, row*6*B(, tail)]
 OP_ROLLBACK = 4      # [OP, model_idx, n, slot*n] — flush before other cmds
 
 
@@ -95,6 +97,109 @@ class GenRequest:
     # length of the slice admitted for the CURRENT step (set by _admit)
     prefill_pos: int = 0
     slice_len: int = 0
+    # extended sampling controls (ops.sample_ex); a request with all of
+    # them at these off values keeps the greedy_sample / topp_sample path
+    top_k: int = 0
+    min_p: float = 0.0
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: Dict[int, float] = field(default_factory=dict)
+    # penalty state: ids of the prompt, and how often each id was
+    # generated (kept by add_token, wherever `generated` grows)
+    prompt_set: Optional[frozenset] = None
+    gen_counts: Dict[int, int] = field(default_factory=dict)
+
+    # whether any control above is on; fixed at construction so that the
+    # per-step routing check costs one attribute read per row
+    extended: bool = field(init=False, default=False)
+
+    def __post_init__(self):
+        if self.prompt_set is None:
+            self.prompt_set = frozenset(self.prompt_tokens)
+        self.extended = bool(
+            self.top_k > 0 or self.min_p > 0.0
+            or self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+            or self.frequency_penalty != 0.0 or self.logit_bias)
+
+    def add_token(self, tok: int) -> None:
+        self.generated.append(tok)
+        self.gen_counts[tok] = self.gen_counts.get(tok, 0) + 1
+
+    def ext_spec(self) -> Optional[Tuple]:
+        """(top_k, min_p, rep, pres, freq, edits) for an extended request,
+        else None. edits lists each touched token once as
+        (token, 2 * count + in_prompt, bias); tokens that no active
+        control can change are left out."""
+        if not self.extended:
+            return None
+        toks = set(self.logit_bias)
+        if self.repetition_penalty != 1.0:
+            toks |= self.prompt_set
+        if (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
+                or self.frequency_penalty != 0.0):
+            toks.update(self.gen_counts)
+        edits = [(t, 2 * self.gen_counts.get(t, 0) + (t in self.prompt_set),
+                  self.logit_bias.get(t, 0.0)) for t in sorted(toks)]
+        return (self.top_k, self.min_p, self.repetition_penalty,
+                self.presence_penalty, self.frequency_penalty, edits)
+
+
+SAMPLING_TOP_K_MAX = 1024
+SAMPLING_MAX_BIASES = 300
+
+
+def parse_sampling_controls(sampling: Dict[str, Any], vocab: int) -> Dict[str, Any]:
+    """Validate the extended sampling keys of a merged sampling dict and
+    return them as GenRequest keyword arguments. Raises ValueError on an
+    ill-typed or out-of-range value."""
+    def num(key, default, lo, hi, lo_open=False):
+        v = sampling.get(key, default)
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"sampling.{key} must be a number, got {v!r}")
+        v = float(v)
+        if (v != v or abs(v) == float("inf") or v > hi or v < lo
+                or (lo_open and v <= lo)):
+            raise ValueError(f"sampling.{key}={v} out of range")
+        return v
+
+    top_k = sampling.get("top_k", 0)
+    if isinstance(top_k, bool) or not isinstance(top_k, int):
+        raise ValueError(f"sampling.top_k must be an integer, got {top_k!r}")
+    if not 0 <= top_k <= SAMPLING_TOP_K_MAX:
+        raise ValueError(
+            f"sampling.top_k={top_k} out of range [0, {SAMPLING_TOP_K_MAX}]")
+    raw = sampling.get("logit_bias") or {}
+    if not isinstance(raw, dict):
+        raise ValueError("sampling.logit_bias must be an object {token_id: bias}")
+    if len(raw) > SAMPLING_MAX_BIASES:
+        raise ValueError(f"sampling.logit_bias has {len(raw)} entries "
+                         f"(max {SAMPLING_MAX_BIASES})")
+    bias: Dict[int, float] = {}
+    for k, v in raw.items():
+        try:
+            t = int(k)
+        except (TypeError, ValueError):
+            raise ValueError(f"sampling.logit_bias key {k!r} is not a token id")
+        if isinstance(k, (bool, float)) or not 0 <= t < vocab:
+            raise ValueError(
+                f"sampling.logit_bias token id {k!r} outside [0, {vocab})")
+        if isinstance(v, bool) or not isinstance(v, (int, float)) \
+                or not -100.0 <= float(v) <= 100.0:
+            raise ValueError(
+                f"sampling.logit_bias[{k}]={v!r} outside [-100, 100]")
+        if t in bias:
+            raise ValueError(f"sampling.logit_bias token id {t} given twice")
+        bias[t] = float(v)
+    return dict(
+        top_k=top_k,
+        min_p=num("min_p", 0.0, 0.0, 1.0),
+        repetition_penalty=num("repetition_penalty", 1.0, 0.0,
+                               float("inf"), lo_open=True),
+        presence_penalty=num("presence_penalty", 0.0, -2.0, 2.0),
+        frequency_penalty=num("frequency_penalty", 0.0, -2.0, 2.0),
+        logit_bias=bias,
+    )
 
 
 @dataclass
@@ -272,6 +377,9 @@ class ModelInstance:
         self._pf_pending: Optional[tuple] = None
         # worker-side speculative mirror: previous step's device sample
         self._spec_worker: Optional[Dict[str, Any]] = None
+        # worker-side: an extended-sampling tail too long for the plan
+        # vector, sent ahead of its OP_DECODE_ASYNC (_send_ext_tail)
+        self._ext_tail: Optional[List[int]] = None
         self._spec: Optional[Dict[str, Any]] = None
         self._graphs: Dict[int, Dict[str, Any]] = {}
         # prefill runs on its own HIP stream so a prefill batch overlaps
@@ -488,6 +596,7 @@ class ModelInstance:
             seeds_eff = [(r.seed + len(r.generated)
                           + (1 if idx[i] >= 0 else 0)) & 0x7FFFFFFFFFFFFFFF
                          for i, r in enumerate(batch)]
+            ext = self._ext_specs(batch)
             if self.tp_size > 1 and self.tp_rank == 0:
                 # async plan: pending rollbacks + per-row feed/sample spec;
                 # workers replicate the launch and sample on-device from
@@ -500,6 +609,8 @@ class ModelInstance:
                             idx[i],
                             seeds_eff[i],
                             _f2i(r.temperature), _f2i(r.top_p)]
+                if ext is not None:
+                    self._send_ext_tail(vec, ext, [r.top_p for r in batch])
                 par.send_ints(vec)
             entry = self._get_graph(bucket)
             # the PREVIOUS step's non-blocking H2D copies read these pinned
@@ -519,6 +630,7 @@ class ModelInstance:
                 if ev is None:
                     ev = entry["h2d_ev"] = torch.cuda.Event()
                 ev.record()
+            pending = None
             if prev is not None and any(x >= 0 for x in idx):
                 gidx = torch.tensor([max(x, 0) for x in idx], dtype=torch.long,
                                     device=dev)
@@ -527,15 +639,20 @@ class ModelInstance:
                 gathered = prev["sampled"].index_select(0, gidx)
                 entry["ids"][:B].copy_(
                     torch.where(mask, gathered, entry["ids"][:B]))
+                if ext is not None:
+                    # a carried-over row's newest token is not in its host
+                    # lists yet: the sampler counts it from the device
+                    pending = torch.where(mask, gathered,
+                                          torch.full_like(gathered, -1))
             if entry["graph"] is not None:
                 entry["graph"].replay()
                 logits = entry["logits"][:B]
             else:  # eager fallback (capture failure / CPU emulation)
                 logits = self._device_decode_fwd(entry["rows"], entry["ids"],
                                                  entry["inc"])[:B]
-            sampled = self._sample_device_params(
+            sampled = self._sample_rows(
                 logits, [r.temperature for r in batch],
-                [r.top_p for r in batch], seeds_eff)
+                [r.top_p for r in batch], seeds_eff, ext, pending)
             kvm.advance_many(seq_ids)
             self.decode_tokens += B
             self.occupancy_acc += B / max(1, self.max_decode_batch)
@@ -625,7 +742,7 @@ class ModelInstance:
                     # invalidated row, or the request died (detach) mid-flight
                     continue
                 t = int(toks[i])
-                r.generated.append(t)
+                r.add_token(t)
                 self._finish_or_run(r, t)
                 if r.done.is_set():
                     # the just-launched step speculatively appended a token
@@ -725,24 +842,70 @@ class ModelInstance:
 
     def _sample_device(self, logits: torch.Tensor,
                        reqs: List[GenRequest]) -> torch.Tensor:
-        return self._sample_device_params(
+        return self._sample_rows(
             logits,
             [r.temperature for r in reqs],
             [r.top_p for r in reqs],
-            [(r.seed + len(r.generated)) & 0x7FFFFFFFFFFFFFFF for r in reqs])
+            [(r.seed + len(r.generated)) & 0x7FFFFFFFFFFFFFFF for r in reqs],
+            self._ext_specs(reqs), None)
+
+    def _sample_rows(self, logits, temps_l, tops_l, seeds_l, ext, pending):
+        """_sample_device_params, called exactly as before extended
+        sampling existed whenever no row is extended."""
+        if ext is None:
+            return self._sample_device_params(logits, temps_l, tops_l, seeds_l)
+        return self._sample_device_params(logits, temps_l, tops_l, seeds_l,
+                                          ext=ext, pending=pending)
+
+    @staticmethod
+    def _ext_specs(reqs: List[GenRequest]) -> Optional[List[Optional[Tuple]]]:
+        """Per-row GenRequest.ext_spec(), or None when no row is extended
+        (the common case: nothing is built)."""
+        if not any(r.extended for r in reqs):
+            return None
+        return [r.ext_spec() for r in reqs]
 
     def _sample_device_params(self, logits: torch.Tensor,
                               temps_l: List[float], tops_l: List[float],
-                              seeds_l: List[int]) -> torch.Tensor:
+                              seeds_l: List[int],
+                              ext: Optional[List[Optional[Tuple]]] = None,
+                              pending: Optional[torch.Tensor] = None,
+                              ) -> torch.Tensor:
         """Param-vector core shared by rank 0 (from GenRequests) and TP
         workers (from the async plan): given bitwise-identical logits and
         the same (temp, top_p, effective-seed) rows, every rank samples
-        the same tokens."""
+        the same tokens.
+
+        ext[i], where not None, is row i's GenRequest.ext_spec(): such
+        rows, greedy or not, form a third group sampled by ops.sample_ex.
+        pending (device int64 [B], -1 = none) holds each row's token that
+        is still in flight on the device (async decode)."""
         B = logits.size(0)
         out = torch.empty(B, dtype=torch.long, device=logits.device)
-        greedy_rows = [i for i in range(B) if temps_l[i] <= 0.0]
-        samp_rows = [i for i in range(B) if temps_l[i] > 0.0]
+        ext_rows = ([i for i in range(B) if ext[i] is not None]
+                    if ext is not None else [])
+        plain = ([i for i in range(B) if ext[i] is None]
+                 if ext_rows else range(B))
+        greedy_rows = [i for i in plain if temps_l[i] <= 0.0]
+        samp_rows = [i for i in plain if temps_l[i] > 0.0]
         lb = logits.to(torch.bfloat16).contiguous()
+        if ext_rows:
+            sub = torch.empty(len(ext_rows), dtype=torch.long,
+                              device=logits.device)
+            specs = [ext[i] for i in ext_rows]
+            whole = len(ext_rows) == B
+            pend = pending
+            if pend is not None and not whole:
+                pend = pend.index_select(0, torch.tensor(
+                    ext_rows, dtype=torch.long, device=logits.device))
+            ops.sample_ex(
+                sub, lb if whole else lb[ext_rows].contiguous(),
+                [temps_l[i] for i in ext_rows], [tops_l[i] for i in ext_rows],
+                [seeds_l[i] for i in ext_rows], [sp[0] for sp in specs],
+                [sp[1] for sp in specs], [sp[2] for sp in specs],
+                [sp[3] for sp in specs], [sp[4] for sp in specs],
+                [sp[5] for sp in specs], pending=pend)
+            out[ext_rows] = sub
         if greedy_rows:
             if len(greedy_rows) == B:
                 ops.greedy_sample(out, lb)
@@ -848,7 +1011,7 @@ class ModelInstance:
         now = time.time()
         with self._lock:
             for r, t in zip(f_reqs, toks):
-                r.generated.append(int(t))
+                r.add_token(int(t))
                 r.first_token_t = now
                 self._finish_or_run(r, int(t))
 
@@ -870,7 +1033,7 @@ class ModelInstance:
             for r, t in zip(f_reqs, toks):
                 if r.done.is_set():
                     continue  # failed/detached while deferred
-                r.generated.append(int(t))
+                r.add_token(int(t))
                 r.first_token_t = now
                 self._finish_or_run(r, int(t))
 
@@ -1083,7 +1246,7 @@ class ModelInstance:
         self.occupancy_acc += len(reqs) / max(1, self.max_decode_batch)
         with self._lock:
             for r, t in zip(reqs, toks):
-                r.generated.append(int(t))
+                r.add_token(int(t))
                 self._finish_or_run(r, int(t))
 
     def _decode_exec(self, plan) -> torch.Tensor:
@@ -1176,6 +1339,7 @@ class ModelInstance:
             seeds_l.append(seed)
             temps_l.append(_i2f(tbits))
             tops_l.append(_i2f(pbits))
+        ext = self._recv_ext_tail(cmd, off + 6 * B, B)
         seq_ids = [kvm.seq_of_slot(s) for s in rows_l]
         kvm.decode_batch_prepare(seq_ids)  # same pages, deterministic
         bucket = min(self._bucket(B), max(self.max_decode_batch, 1))
@@ -1193,6 +1357,7 @@ class ModelInstance:
                 ev = entry["h2d_ev"] = torch.cuda.Event()
             ev.record()
         prev = self._spec_worker
+        pending = None
         if prev is not None and any(x >= 0 for x in idx_l):
             dev = self.device
             gidx = torch.tensor([max(x, 0) for x in idx_l], dtype=torch.long,
@@ -1202,16 +1367,66 @@ class ModelInstance:
             gathered = prev["sampled"].index_select(0, gidx)
             entry["ids"][:B].copy_(torch.where(mask, gathered,
                                                entry["ids"][:B]))
+            if ext is not None:
+                pending = torch.where(mask, gathered,
+                                      torch.full_like(gathered, -1))
         if entry["graph"] is not None:
             entry["graph"].replay()
             logits = entry["logits"][:B]
         else:
             logits = self._device_decode_fwd(entry["rows"], entry["ids"],
                                              entry["inc"])[:B]
-        sampled = self._sample_device_params(logits, temps_l, tops_l, seeds_l)
+        sampled = self._sample_rows(logits, temps_l, tops_l, seeds_l, ext,
+                                    pending)
         kvm.advance_many(seq_ids)
         self.decode_tokens += B
         self._spec_worker = {"sampled": sampled}
+
+    def _send_ext_tail(self, vec: List[int], ext: List[Optional[Tuple]],
+                       tops_l: List[float]) -> None:
+        """Append the extended-sampling tail to an OP_DECODE_ASYNC vector:
+        n_ext, then per extended row [row, top_k, bits(min_p, rep, pres,
+        freq, top_p), n_edits, (tok, cnt, bias bits) * n_edits]. A tail too
+        long for the fixed plan buffer (long prompts under a repetition
+        penalty) travels ahead as a pickled command and the vector carries
+        n_ext = -1."""
+        rows = [i for i, sp in enumerate(ext) if sp is not None]
+        tail = [len(rows)]
+        for i in rows:
+            top_k, min_p, rep, pres, freq, edits = ext[i]
+            tail += [i, top_k, _f2i(min_p), _f2i(rep), _f2i(pres), _f2i(freq),
+                     _f2i(tops_l[i]), len(edits)]
+            for t, c, b in edits:
+                tail += [t, c, _f2i(b)]
+        if 1 + len(vec) + len(tail) <= par.PLAN_CAP:
+            vec += tail
+        else:
+            par.broadcast_obj(("ext_tail", self.name, tail))
+            vec.append(-1)
+
+    def _recv_ext_tail(self, cmd: List[int], off: int,
+                       B: int) -> Optional[List[Optional[Tuple]]]:
+        """Worker half of _send_ext_tail: per-row ext specs, or None when
+        the plan has no tail (no extended row in this step)."""
+        if off >= len(cmd):
+            return None
+        if cmd[off] < 0:
+            tail, self._ext_tail = self._ext_tail, None
+            off = 0
+        else:
+            tail = cmd
+        n_ext = tail[off]
+        off += 1
+        ext: List[Optional[Tuple]] = [None] * B
+        for _ in range(n_ext):
+            i, top_k, mp, rep, pres, freq, _tp, n = tail[off:off + 8]
+            off += 8
+            edits = [(tail[off + 3 * k], tail[off + 3 * k + 1],
+                      _i2f(tail[off + 3 * k + 2])) for k in range(n)]
+            off += 3 * n
+            ext[i] = (top_k, _i2f(mp), _i2f(rep), _i2f(pres), _i2f(freq),
+                      edits)
+        return ext
 
     def _finish_or_run(self, r: GenRequest, tok: int):
         """Called with lock held, after appending tok."""
@@ -1639,8 +1854,15 @@ class LLMEngine:
         sampling = dict(agent.sampling or {})
         sampling.update(kwargs)
         trace_id = str(sampling.pop("trace_id", ""))
+        # raises before anything is enqueued: a bad value is the client's
+        # error, never a pending WAL entry
+        try:
+            controls = parse_sampling_controls(sampling, inst.cfg.vocab_size)
+        except ValueError as exc:
+            raise InvalidSampling(str(exc)) from None
         prompt = self._build_prompt(agent, message)
         req = GenRequest(
+            **controls,
             agent_id=agent_id,
             prompt_tokens=inst.tokenizer.encode(prompt),
             max_new=int(sampling.get("max_tokens", DEFAULT_MAX_NEW)),
@@ -1909,6 +2131,8 @@ class LLMEngine:
             inst = self._instances[cmd[1]]
             if op == "prefill":
                 inst._prefill_exec(cmd[2])
+            elif op == "ext_tail":
+                inst._ext_tail = cmd[2]  # consumed by the next async plan
             elif op == "decode":
                 inst._decode_exec(cmd[2])
             elif op == "bind":

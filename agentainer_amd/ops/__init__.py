@@ -171,6 +171,66 @@ def topp_sample(out, logits, temps, top_ps, seeds):
     return out
 
 
+_sample_ws_cache = {}
+
+
+def _sample_ws(device, n: int) -> torch.Tensor:
+    # keyed like _lora_ws: the deferred prefill sample and the decode
+    # sample may run on different streams
+    stream = (torch.cuda.current_stream(device).cuda_stream
+              if device.type == "cuda" else 0)
+    key = (device, stream)
+    ws = _sample_ws_cache.get(key)
+    if ws is None or ws.numel() < n:
+        ws = torch.empty(n, dtype=torch.float32, device=device)
+        _sample_ws_cache[key] = ws
+    return ws
+
+
+def sample_ex(out, logits, temps, top_ps, seeds, top_ks, min_ps, reps, press,
+              freqs, edits, pending=None, ws=None):
+    """Extended sampler: penalties, logit_bias, top-k, min-p, top-p
+    (semantics: reference.sample_ex). logits bf16 [B, V]; the scalar
+    parameters are per-row Python sequences; edits[b] is a sequence of
+    (token, 2 * count + in_prompt, bias) with unique tokens; pending is a
+    device int64 [B] of in-flight tokens (-1: none) or None. Each CSR
+    array goes to the device in one copy. ws (f32, >= B*V) receives the
+    edited rows; by default a cached per-(device, stream) workspace."""
+    B, V = logits.shape
+    dev = logits.device
+    ptr = [0]
+    tok, cnt, bias = [], [], []
+    for row in edits:
+        if row:
+            t, c, b = zip(*row)
+            tok.extend(t); cnt.extend(c); bias.extend(b)
+        ptr.append(len(tok))
+    assert len(ptr) == B + 1
+
+    def vec(vals, dtype):
+        return torch.tensor(list(vals), dtype=dtype).to(dev, non_blocking=True)
+
+    args = (vec(temps, torch.float32), vec(top_ps, torch.float32),
+            vec(min_ps, torch.float32), vec(reps, torch.float32),
+            vec(press, torch.float32), vec(freqs, torch.float32),
+            vec(top_ks, torch.int32), vec(seeds, torch.int64),
+            vec(ptr, torch.int32), vec(tok, torch.int32),
+            vec(cnt, torch.int32), vec(bias, torch.float32))
+    if pending is None:
+        pending = torch.full((B,), -1, dtype=torch.int64, device=dev)
+    mod = _dispatch("sample_ex", logits)
+    if mod:
+        if ws is None:
+            ws = _sample_ws(dev, B * V)
+        logits = logits.contiguous()
+        if logits.data_ptr() % 16:  # a view into a larger buffer
+            logits = logits.clone()
+        mod.sample_ex(out, logits, ws, *args, pending)
+    else:
+        reference.sample_ex(out, logits, ws, *args, pending)
+    return out
+
+
 _ws_cache = {}
 _EMPTY_WS = {}
 SKINNY_DISABLED = os.environ.get("AGENTAINER_DISABLE_SKINNY", "0") == "1"

@@ -40,6 +40,7 @@ SOURCES = [
     "decode_attn.hip",
     "prefill_attn.hip",
     "sampling.hip",
+    "sample_ex.hip",
     "skinny_gemm.hip",
     "lora.hip",
 ]

@@ -25,6 +25,13 @@ void paged_prefill_attention(torch::Tensor out, torch::Tensor q,
 void greedy_sample(torch::Tensor out, torch::Tensor logits);
 void topp_sample(torch::Tensor out, torch::Tensor logits, torch::Tensor temps,
                  torch::Tensor top_ps, torch::Tensor seeds);
+void sample_ex(torch::Tensor out, torch::Tensor logits, torch::Tensor ws,
+               torch::Tensor temps, torch::Tensor top_ps, torch::Tensor min_ps,
+               torch::Tensor reps, torch::Tensor press, torch::Tensor freqs,
+               torch::Tensor top_ks, torch::Tensor seeds,
+               torch::Tensor edit_ptr, torch::Tensor edit_tok,
+               torch::Tensor edit_cnt, torch::Tensor edit_bias,
+               torch::Tensor pending_tok);
 void gather_kv_pages(torch::Tensor dst, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor page_ids);
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -66,6 +73,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "varlen causal MFMA attention over the paged KV cache");
   m.def("greedy_sample", &greedy_sample, "argmax over vocab per row");
   m.def("topp_sample", &topp_sample, "temperature + top-p sampling per row");
+  m.def("sample_ex", &sample_ex,
+        "penalties + logit_bias + exact top-k/min-p/top-p sampling per row");
   m.def("gather_kv_pages", &gather_kv_pages, "pages -> host-shaped buffer");
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm,
         "residual += bf16(sum_s ws[s]); rmsnorm");

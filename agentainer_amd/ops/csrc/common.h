@@ -101,3 +101,12 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, WAVE));
   return v;
 }
+
+// xorshift128 per row seeded from (seed, row) — deterministic across replays.
+// Shared by the samplers; ops/reference.py::uniform01 is its integer port.
+__device__ __forceinline__ float uniform01(unsigned long long seed, int row) {
+  unsigned long long x = seed ^ (0x9e3779b97f4a7c15ull * (row + 1));
+  x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
+  x *= 0x2545F4914F6CDD1Dull;
+  return (float)((x >> 40) & 0xFFFFFF) / 16777216.0f;
+}

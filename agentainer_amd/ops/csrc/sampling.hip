@@ -70,14 +70,6 @@ __global__ __launch_bounds__(256) void greedy_kernel(
   }
 }
 
-// xorshift128 per row seeded from (seed, row) — deterministic across replays
-__device__ __forceinline__ float uniform01(unsigned long long seed, int row) {
-  unsigned long long x = seed ^ (0x9e3779b97f4a7c15ull * (row + 1));
-  x ^= x >> 12; x ^= x << 25; x ^= x >> 27;
-  x *= 0x2545F4914F6CDD1Dull;
-  return (float)((x >> 40) & 0xFFFFFF) / 16777216.0f;
-}
-
 __global__ __launch_bounds__(256) void topp_kernel(
     long* __restrict__ out, const short* __restrict__ logits,
     const float* __restrict__ temps, const float* __restrict__ top_ps,

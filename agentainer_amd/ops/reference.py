@@ -158,6 +158,128 @@ def topp_sample(out: torch.Tensor, logits: torch.Tensor, temps: torch.Tensor,
         out[b] = pick.to(out.device)
 
 
+SAMPLE_EX_CAP = 1024  # candidate capacity of the extended sampler
+_M64 = (1 << 64) - 1
+
+
+def uniform01(seed: int, row: int) -> float:
+    """Integer port of the kernels' per-row hash (csrc/common.h): the
+    CPU reference and the GPU draw from the same u for (seed, row)."""
+    x = ((int(seed) & _M64) ^ (0x9E3779B97F4A7C15 * (int(row) + 1))) & _M64
+    x ^= x >> 12
+    x ^= (x << 25) & _M64
+    x ^= x >> 27
+    x = (x * 0x2545F4914F6CDD1D) & _M64
+    return ((x >> 40) & 0xFFFFFF) / 16777216.0
+
+
+def sample_ex_edit_row(logits_row: torch.Tensor, rep: float, pres: float,
+                       freq: float, toks, cnts, biases,
+                       pending: int = -1) -> torch.Tensor:
+    """The edited f32 logits of one row (the kernel's workspace row).
+    toks are unique; cnts[i] = 2 * c + in_prompt; pending (-1: none) is
+    one more generated occurrence that the host lists do not hold yet."""
+    V = logits_row.numel()
+    l = logits_row.detach().float().cpu().clone()
+    toks = [int(t) for t in toks]
+    cnts = [int(c) for c in cnts]
+    biases = [float(b) for b in biases]
+    if 0 <= pending < V:
+        if pending in toks:
+            cnts[toks.index(pending)] += 2
+        else:
+            toks.append(int(pending)); cnts.append(2); biases.append(0.0)
+    if not toks:
+        return l
+    idx = torch.tensor(toks, dtype=torch.long)
+    cnt = torch.tensor(cnts, dtype=torch.int64)
+    c = (cnt >> 1).to(torch.float32)
+    v = l[idx]
+    f32 = lambda x: torch.tensor(float(x), dtype=torch.float32)
+    # 1. repetition (sign-dependent), 2. frequency + presence, 3. bias;
+    # every step rounds to f32, as the kernel's explicit roundings do
+    v = torch.where(cnt > 0, torch.where(v > 0, v / f32(rep), v * f32(rep)), v)
+    pen = f32(freq) * c + torch.where(c > 0, f32(pres), f32(0.0))
+    v = v - pen
+    v = v + torch.tensor(biases, dtype=torch.float32)
+    l[idx] = v
+    return l
+
+
+def sample_ex_kept(edited: torch.Tensor, temp: float, top_p: float,
+                   min_p: float, top_k: int):
+    """float64 selection of one sampled row: (ids of the kept prefix in
+    (p desc, id asc) order, their cumulative p)."""
+    V = edited.numel()
+    s = edited.double() / float(temp)
+    p = torch.exp(s - s.max())
+    total = p.sum()
+    n0 = min(int(top_k) if int(top_k) > 0 else SAMPLE_EX_CAP, SAMPLE_EX_CAP, V)
+    # stable sort on -p keeps ascending ids among equal p
+    order = torch.sort(-p, stable=True).indices[:n0]
+    sp = p[order]
+    n_minp = int((sp >= float(min_p) * sp[0]).sum())
+    cum = sp.cumsum(0)
+    n_topp = n0
+    if float(top_p) < 1.0:
+        hit = (cum / total >= float(top_p)).nonzero()
+        if hit.numel():
+            n_topp = int(hit[0]) + 1
+    keep = max(1, min(n0, n_minp, n_topp))
+    return order[:keep], cum[:keep]
+
+
+def sample_ex(out: torch.Tensor, logits: torch.Tensor, ws, temps, top_ps,
+              min_ps, reps, press, freqs, top_ks, seeds, edit_ptr, edit_tok,
+              edit_cnt, edit_bias, pending_tok, rows=None) -> None:
+    """Definition of the extended sampler (csrc/sample_ex.hip follows it).
+
+    Per row, in f32 on the bf16 logit l of token t, with seen(t) = t is in
+    the request's prompt or was generated, c(t) = times generated:
+      1. seen:  l = l / rep if l > 0 else l * rep
+      2. l -= freq * c + pres * (c > 0)
+      3. l += bias(t)
+    The edits come as CSR rows of unique tokens with
+    edit_cnt = 2 * c + in_prompt; pending_tok[b] >= 0 counts as one more
+    generated occurrence (async decode: the newest token is still on the
+    device). temperature <= 0 takes the argmax of the edited row, lowest
+    id on ties. Otherwise s = l / T, p = exp(s - max), total = sum of p
+    over the whole row; tokens are sorted by (p desc, id asc); the
+    candidates are the first n0 = min(top_k or 1024, 1024, V); the kept
+    prefix has length min(n0, n_minp, n_topp) with n_minp the count of
+    candidates with p >= min_p * p_max and n_topp the smallest n whose
+    cumulative p / total >= top_p (top_p >= 1: no nucleus cut); the draw
+    is the inverse CDF over the kept prefix at u = uniform01(seed, row).
+
+    Known limitation: a nucleus wider than 1024 tokens is truncated to
+    the top 1024 (topp_sample truncates at 512).
+
+    rows: the row index hashed with each seed (default: the batch index,
+    as the kernel uses). ws, when given, receives the edited f32 rows."""
+    B, V = logits.shape
+    ptr = [int(x) for x in edit_ptr.tolist()]
+    tok = edit_tok.tolist()
+    cnt = edit_cnt.tolist()
+    bias = edit_bias.tolist()
+    pend = [int(x) for x in pending_tok.tolist()]
+    for b in range(B):
+        e0, e1 = ptr[b], ptr[b + 1]
+        l = sample_ex_edit_row(logits[b], float(reps[b]), float(press[b]),
+                               float(freqs[b]), tok[e0:e1], cnt[e0:e1],
+                               bias[e0:e1], pend[b])
+        if ws is not None:
+            ws.view(-1)[b * V:(b + 1) * V] = l.to(ws.device)
+        T = float(temps[b])
+        if T <= 0.0:
+            out[b] = int(l.argmax())  # first maximal index
+            continue
+        ids, cum = sample_ex_kept(l, T, float(top_ps[b]), float(min_ps[b]),
+                                  int(top_ks[b]))
+        u = uniform01(int(seeds[b]), b if rows is None else int(rows[b]))
+        j = int(torch.searchsorted(cum, u * float(cum[-1])))
+        out[b] = int(ids[min(j, ids.numel() - 1)])
+
+
 def gather_kv_pages(dst: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, page_ids: torch.Tensor) -> None:
     n_kv = k_cache.size(1)

@@ -88,6 +88,7 @@ _plan_group = None
 # op + args + up to 4096 async rows at 6 ints each (gloo broadcast is
 # latency-bound — 128 B and 192 KB cost the same, tools/plan_latency.py)
 _PLAN_CAP = 64 + 6 * 4096
+PLAN_CAP = _PLAN_CAP  # senders check 1 + len(vec) against this
 _plan_buf: Optional[torch.Tensor] = None
 _OP_PICKLE = 0  # engine op codes start at 1 (llm.OP_*)
 

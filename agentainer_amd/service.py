@@ -31,7 +31,7 @@ from typing import Any, Dict, Optional, Tuple
 
 from .backup import BackupManager
 from .config import Config, load_config
-from .engine.base import ModelNotFound
+from .engine.base import InvalidSampling, ModelNotFound
 from .engine.echo import EchoEngine
 from .health import HealthMonitor
 from .logs import Logger, set_global_logger
@@ -182,6 +182,14 @@ class Runtime:
                          "message": f"agent unavailable: {exc}",
                          "data": {"request_id": req.id if req else None,
                                   "status": "pending"}}
+        except InvalidSampling as exc:
+            # the client's error: failed now, nothing left to replay
+            if req is not None:
+                self.requests.mark_failed(agent_id, req.id, str(exc),
+                                          final=True)
+            return 400, {"success": False, "message": str(exc),
+                         "data": {"request_id": req.id if req else None,
+                                  "status": "failed"}}
         except Exception as exc:  # noqa: BLE001
             if req is not None:
                 self.requests.mark_failed(agent_id, req.id, str(exc))
@@ -242,7 +250,9 @@ class Runtime:
                 return
             except Exception as exc:  # noqa: BLE001
                 if req is not None:
-                    self.requests.mark_failed(agent_id, req.id, str(exc))
+                    self.requests.mark_failed(
+                        agent_id, req.id, str(exc),
+                        final=isinstance(exc, InvalidSampling))
                 yield {"error": str(exc),
                        "request_id": req.id if req else None}
                 return

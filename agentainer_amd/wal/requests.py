@@ -133,7 +133,10 @@ class RequestManager:
         self.store.flush()
         return req
 
-    def mark_failed(self, agent_id: str, req_id: str, error: str) -> Optional[Request]:
+    def mark_failed(self, agent_id: str, req_id: str, error: str,
+                    final: bool = False) -> Optional[Request]:
+        """Count one failed attempt; dead-letter after max_retries, or at
+        once when final (a request no replay can ever serve)."""
         req = self.get(agent_id, req_id)
         if req is None:
             return None
@@ -141,7 +144,7 @@ class RequestManager:
             return req  # completed/dead-lettered records never regress
         req.retry_count += 1
         req.error = error
-        if req.retry_count >= req.max_retries:
+        if final or req.retry_count >= req.max_retries:
             # dead-letter (requests.go:227-275)
             req.status = FAILED
             req.processed_at = time.time()
