@@ -37,6 +37,9 @@ from .. import parallel as par
 from ..store import Store
 from .base import InvalidSampling, ModelNotFound
 from .kvcache import KVCacheManager, KVCheckpoint, OutOfPages
+from . import plan as wire
+from .plan import (OP_BARRIER, OP_DECODE, OP_DECODE_ASYNC, OP_ROLLBACK,
+                   AsyncDecodePlan)
 from .tokenizer import ByteTokenizer
 from ..models.llama import (AttnMetadata, LLAMA_CONFIGS, LlamaConfig,
                             LlamaForCausalLM)
@@ -44,31 +47,10 @@ from ..models.lora import LoraContext, LoraError, LoraPool, adapter_key
 
 DEFAULT_MAX_NEW = 64
 
-# int-vector op codes on the TP plan channel (parallel.dist.send_ints);
-# 0 is reserved for pickled commands
-OP_DECODE = 1   # [OP, model_idx, B, slot*B, token*B] — the per-step hot path
-OP_BARRIER = 2  # [OP] — timing fence (bench.py --tp)
-# async (speculative) decode: rollbacks from the previous resolve are
-# prepended, then per-row (slot, token|-1, prev_idx, eff_seed, temp_bits,
-# top_p_bits) — workers feed carried-over rows from their OWN previous
-# device sample (logits are bitwise-identical across ranks after the
-# all-reduce, and sampling is seed-deterministic, so every rank samples
-# the same token without any extra communication)
-# When a row uses the extended sampling controls a tail follows the 6*B
-# block (ModelInstance._send_ext_tail); without one the vector is unchanged.
-OP_DECODE_ASYNC = 3  # [OP, model_idx, B, nrb, rb_slot*nrb, row*6*B(, tail)]
-OP_ROLLBACK = 4      # [OP, model_idx, n, slot*n] — flush before other cmds
 
-
-def _f2i(x: float) -> int:
-    """float32 bit pattern as int (plan-channel encoding)."""
-    import struct
-    return struct.unpack("<I", struct.pack("<f", float(x)))[0]
-
-
-def _i2f(x: int) -> float:
-    import struct
-    return struct.unpack("<f", struct.pack("<I", int(x) & 0xFFFFFFFF))[0]
+def _ema_next(ema: float, ms: float) -> float:
+    """The moving average behind every *_ms stats figure."""
+    return 0.05 * ms + 0.95 * ema
 
 
 class EngineDead(RuntimeError):
@@ -376,9 +358,9 @@ class ModelInstance:
         # deferred prefill sample (async engines): (logits, final_reqs)
         self._pf_pending: Optional[tuple] = None
         # worker-side speculative mirror: previous step's device sample
-        self._spec_worker: Optional[Dict[str, Any]] = None
+        self._spec_worker: Optional[torch.Tensor] = None
         # worker-side: an extended-sampling tail too long for the plan
-        # vector, sent ahead of its OP_DECODE_ASYNC (_send_ext_tail)
+        # vector, sent ahead of its OP_DECODE_ASYNC (plan.encode_async)
         self._ext_tail: Optional[List[int]] = None
         self._spec: Optional[Dict[str, Any]] = None
         self._graphs: Dict[int, Dict[str, Any]] = {}
@@ -523,8 +505,8 @@ class ModelInstance:
             self.steps += 1 if ran else 0
             if ran:  # EMA of wall step time (engine-side diagnostics)
                 dt = (time.time() - self._step_started) * 1000.0
-                self._step_ms_ema = (0.05 * dt
-                                     + 0.95 * getattr(self, "_step_ms_ema", dt))
+                self._step_ms_ema = _ema_next(
+                    getattr(self, "_step_ms_ema", dt), dt)
             self._step_started = None
             self.last_step_t = time.time()
             return ran
@@ -557,13 +539,13 @@ class ModelInstance:
     def _phase_mark(self, key: str, t0: float) -> float:
         """EMA per-phase wall times (stats diagnostics); returns now."""
         now = time.time()
-        ema = self._phase_ms.get(key, 0.0)
-        self._phase_ms[key] = 0.05 * (now - t0) * 1000.0 + 0.95 * ema
+        self._ema(key, (now - t0) * 1000.0)
         return now
 
+    def _ema(self, key: str, ms: float) -> None:
+        self._phase_ms[key] = _ema_next(self._phase_ms.get(key, 0.0), ms)
+
     def _step_async(self) -> bool:
-        kvm = self.kvm
-        dev = self.device
         t0 = time.time()
         # phase 0: publish last step's deferred prefill sample, so those
         # rows are in `running` for this step's snapshot (same step they
@@ -577,15 +559,13 @@ class ModelInstance:
         with self._lock:
             batch = [r for r in self.running if not r.done.is_set()]
         launched = None
+        prev = self._spec
         if batch:
             bucket = min(self._bucket(len(batch)), max(self.max_decode_batch, 1))
             if len(batch) > bucket:
                 batch = batch[:bucket]
                 self._rotate_running(batch)
-            B = len(batch)
             seq_ids = [self._bindings[r.agent_id].seq_id for r in batch]
-            rows = kvm.decode_batch_prepare(seq_ids)
-            prev = self._spec
             pos = {id(r): i for i, r in enumerate(prev["reqs"])} if prev else {}
             idx = [pos.get(id(r), -1) for r in batch]
             # effective sampling seed: a carried-over row has ONE unresolved
@@ -596,69 +576,26 @@ class ModelInstance:
             seeds_eff = [(r.seed + len(r.generated)
                           + (1 if idx[i] >= 0 else 0)) & 0x7FFFFFFFFFFFFFFF
                          for i, r in enumerate(batch)]
-            ext = self._ext_specs(batch)
+            plan = AsyncDecodePlan(
+                slots=[self.kvm.slot(s) for s in seq_ids],
+                feed=[r.generated[-1] if idx[i] < 0 else -1
+                      for i, r in enumerate(batch)],
+                prev_idx=idx, seeds=seeds_eff,
+                temps=[r.temperature for r in batch],
+                tops=[r.top_p for r in batch],
+                ext=self._ext_specs(batch),
+                rollbacks=self._take_rollbacks())
             if self.tp_size > 1 and self.tp_rank == 0:
                 # async plan: pending rollbacks + per-row feed/sample spec;
                 # workers replicate the launch and sample on-device from
                 # their own identical logits (no return traffic)
-                rb, self._pending_rb = self._pending_rb, []
-                vec = [OP_DECODE_ASYNC, self._model_idx, B, len(rb)] + rb
-                for i, r in enumerate(batch):
-                    vec += [rows[i],
-                            r.generated[-1] if idx[i] < 0 else -1,
-                            idx[i],
-                            seeds_eff[i],
-                            _f2i(r.temperature), _f2i(r.top_p)]
-                if ext is not None:
-                    self._send_ext_tail(vec, ext, [r.top_p for r in batch])
-                par.send_ints(vec)
-            entry = self._get_graph(bucket)
-            # the PREVIOUS step's non-blocking H2D copies read these pinned
-            # staging buffers; wait for that DMA before rewriting them (a
-            # torn read would feed wrong slots/tokens into the graph)
-            ev = entry.get("h2d_ev") if self.is_gpu else None
-            if ev is not None:
-                ev.synchronize()
-            entry["rows_pin"][:B] = torch.tensor(rows, dtype=torch.long)
-            entry["rows_pin"][B:] = self._pad_slot
-            entry["rows"].copy_(entry["rows_pin"], non_blocking=True)
-            entry["ids_pin"][:B] = torch.tensor(
-                [r.generated[-1] if idx[i] < 0 else 0
-                 for i, r in enumerate(batch)], dtype=torch.long)
-            entry["ids"][:B].copy_(entry["ids_pin"][:B], non_blocking=True)
-            if self.is_gpu:
-                if ev is None:
-                    ev = entry["h2d_ev"] = torch.cuda.Event()
-                ev.record()
-            pending = None
-            if prev is not None and any(x >= 0 for x in idx):
-                gidx = torch.tensor([max(x, 0) for x in idx], dtype=torch.long,
-                                    device=dev)
-                mask = torch.tensor([x >= 0 for x in idx], dtype=torch.bool,
-                                    device=dev)
-                gathered = prev["sampled"].index_select(0, gidx)
-                entry["ids"][:B].copy_(
-                    torch.where(mask, gathered, entry["ids"][:B]))
-                if ext is not None:
-                    # a carried-over row's newest token is not in its host
-                    # lists yet: the sampler counts it from the device
-                    pending = torch.where(mask, gathered,
-                                          torch.full_like(gathered, -1))
-            if entry["graph"] is not None:
-                entry["graph"].replay()
-                logits = entry["logits"][:B]
-            else:  # eager fallback (capture failure / CPU emulation)
-                logits = self._device_decode_fwd(entry["rows"], entry["ids"],
-                                                 entry["inc"])[:B]
-            sampled = self._sample_rows(
-                logits, [r.temperature for r in batch],
-                [r.top_p for r in batch], seeds_eff, ext, pending)
-            kvm.advance_many(seq_ids)
-            self.decode_tokens += B
-            self.occupancy_acc += B / max(1, self.max_decode_batch)
+                par.send_ints(wire.encode_async(self._model_idx, self.name,
+                                                plan))
+            sampled = self._run_async_plan(
+                plan, prev["sampled"] if prev else None, seq_ids)
+            self.occupancy_acc += len(batch) / max(1, self.max_decode_batch)
             launched = {"reqs": batch, "sampled": sampled, "invalid": set()}
         t0 = self._phase_mark("p1_launch_ms", t0)
-        prev = self._spec
         self._spec = launched
 
         # phase 2: RESOLVE the previous step's tokens on the host while the
@@ -672,24 +609,21 @@ class ModelInstance:
         admitted = self._admit()
         t0 = self._phase_mark("p3_admit_ms", t0)
         if admitted:
-            if self._prefill_stream is not None:
-                if self._pages_freed:
-                    # pages freed by a reset/rollback may be re-allocated by
-                    # this prefill while the in-flight decode still writes
-                    # its (rolled-back) speculative K/V there — serialize
-                    # the streams for this one step
-                    self._prefill_stream.wait_stream(torch.cuda.current_stream())
-                    self._pages_freed = False
-                try:
+            if self._prefill_stream is not None and self._pages_freed:
+                # pages freed by a reset/rollback may be re-allocated by
+                # this prefill while the in-flight decode still writes
+                # its (rolled-back) speculative K/V there — serialize
+                # the streams for this one step
+                self._prefill_stream.wait_stream(torch.cuda.current_stream())
+                self._pages_freed = False
+            try:
+                if self._prefill_stream is not None:
                     with torch.cuda.stream(self._prefill_stream):
                         self._prefill(admitted)
-                except OutOfPages as e:
-                    self._fail_prefill(admitted, str(e))
-            else:
-                try:
+                else:
                     self._prefill(admitted)
-                except OutOfPages as e:
-                    self._fail_prefill(admitted, str(e))
+            except OutOfPages as e:
+                self._fail_prefill(admitted, str(e))
             self._phase_mark("p3_prefill_ms", t0)
         return bool(batch) or bool(admitted) or prev is not None or had_pf
 
@@ -928,13 +862,21 @@ class ModelInstance:
 
     def _bcast(self, cmd):
         if self.tp_size > 1 and self.tp_rank == 0:
-            if self._pending_rb:
-                # flush speculative rollbacks FIRST: the command below may
-                # read KV state (prefill positions, unbind) that is only
-                # consistent across ranks once workers applied them
-                rb, self._pending_rb = self._pending_rb, []
-                par.send_ints([OP_ROLLBACK, self._model_idx, len(rb)] + rb)
+            # flush speculative rollbacks FIRST: the command below may
+            # read KV state (prefill positions, unbind) that is only
+            # consistent across ranks once workers applied them
+            self._flush_rollbacks()
             par.broadcast_obj(cmd)
+
+    def _take_rollbacks(self) -> List[int]:
+        rb, self._pending_rb = self._pending_rb, []
+        return rb
+
+    def _flush_rollbacks(self) -> None:
+        """Rank 0: pending rollbacks as a command of their own."""
+        if self._pending_rb:
+            par.send_ints(wire.encode_rollback(self._model_idx,
+                                               self._take_rollbacks()))
 
     def _prefill(self, reqs: List[GenRequest]):
         t0 = time.time()
@@ -1005,29 +947,11 @@ class ModelInstance:
             return
         toks = self._sample(logits, f_reqs)  # host sync point
         self._phase_mark("pf_sample_ms", t0)
-        ema = self._phase_ms.get("pf_cpu_ms", 0.0)
-        self._phase_ms["pf_cpu_ms"] = (0.05 * (time.thread_time() - c0) * 1000.0
-                                       + 0.95 * ema)
-        now = time.time()
-        with self._lock:
-            for r, t in zip(f_reqs, toks):
-                r.add_token(int(t))
-                r.first_token_t = now
-                self._finish_or_run(r, int(t))
+        self._ema("pf_cpu_ms", (time.thread_time() - c0) * 1000.0)
+        self._publish_prefill(f_reqs, toks)
 
-    def _resolve_prefill(self) -> None:
-        """Sample + publish a deferred prefill (see _prefill). Runs at the
-        head of the next step and at every drain point, so no checkpoint
-        or unbind ever observes an unsampled prefill."""
-        pend = self._pf_pending
-        if pend is None:
-            return
-        self._pf_pending = None
-        logits, f_reqs = pend
-        if self._prefill_stream is not None:
-            # order the sampling kernels after the side-stream producer
-            torch.cuda.current_stream().wait_stream(self._prefill_stream)
-        toks = self._sample(logits, f_reqs)
+    def _publish_prefill(self, f_reqs: List[GenRequest], toks) -> None:
+        """Hand each finished prefill its first token."""
         now = time.time()
         with self._lock:
             for r, t in zip(f_reqs, toks):
@@ -1036,6 +960,18 @@ class ModelInstance:
                 r.add_token(int(t))
                 r.first_token_t = now
                 self._finish_or_run(r, int(t))
+
+    def _resolve_prefill(self) -> None:
+        """Sample + publish a deferred prefill (see _prefill). Runs at the
+        head of the next step and at every drain point, so no checkpoint
+        or unbind ever observes an unsampled prefill."""
+        if self._pf_pending is None:
+            return
+        (logits, f_reqs), self._pf_pending = self._pf_pending, None
+        if self._prefill_stream is not None:
+            # order the sampling kernels after the side-stream producer
+            torch.cuda.current_stream().wait_stream(self._prefill_stream)
+        self._publish_prefill(f_reqs, self._sample(logits, f_reqs))
 
     @staticmethod
     def _prefill_bucket(n: int) -> int:
@@ -1141,11 +1077,9 @@ class ModelInstance:
         c0 = time.thread_time()
         out = self._forward(input_ids, md, last_rows, lora)
         fwd_cpu = (time.thread_time() - c0) * 1000.0
-        ema = self._phase_ms.get("pf_fwd_cpu_ms", 0.0)
-        self._phase_ms["pf_fwd_cpu_ms"] = 0.05 * fwd_cpu + 0.95 * ema
-        mn = self._phase_ms.get("pf_fwd_cpu_min_ms")
-        if mn is None or fwd_cpu < mn:
-            self._phase_ms["pf_fwd_cpu_min_ms"] = fwd_cpu
+        self._ema("pf_fwd_cpu_ms", fwd_cpu)
+        self._phase_ms["pf_fwd_cpu_min_ms"] = min(
+            fwd_cpu, self._phase_ms.get("pf_fwd_cpu_min_ms", fwd_cpu))
         return out
 
     def _forward(self, input_ids, md, last_rows, lora) -> torch.Tensor:
@@ -1230,16 +1164,13 @@ class ModelInstance:
         plan = [(self._bindings[r.agent_id].seq_id, r.generated[-1])
                 for r in reqs]
         if self.tp_size > 1 and self.tp_rank == 0:
-            if self._pending_rb:  # async->eager fallback edge
-                rb, self._pending_rb = self._pending_rb, []
-                par.send_ints([OP_ROLLBACK, self._model_idx, len(rb)] + rb)
+            self._flush_rollbacks()  # async->eager fallback edge
             # binary hot path: ONE int-tensor broadcast on the gloo plan
             # channel (slot ids are deterministic across ranks), replacing
             # the round-1 per-step pickled broadcast_object_list
-            vec = [OP_DECODE, self._model_idx, len(plan)]
-            vec.extend(self.kvm.slot(s) for s, _t in plan)
-            vec.extend(t for _s, t in plan)
-            par.send_ints(vec)
+            par.send_ints(wire.encode_sync(
+                self._model_idx, [self.kvm.slot(s) for s, _t in plan],
+                [t for _s, t in plan]))
         logits = self._decode_exec(plan)
         toks = self._sample(logits, reqs)
         self.decode_tokens += len(reqs)
@@ -1278,155 +1209,100 @@ class ModelInstance:
         return self._forward(input_ids, md, None, lora)
 
     def _decode_exec_gpu(self, plan) -> torch.Tensor:
-        kvm = self.kvm
-        B = len(plan)
-        bucket = min(self._bucket(B), max(self.max_decode_batch, 1))
+        seq_ids = [s for s, _t in plan]
         # host half of the append, one lock for the whole batch
-        row_ids = kvm.decode_batch_prepare([s for s, _t in plan])
-        entry = self._get_graph(bucket)
-        # TP workers run ahead with no host sync per step: wait out the
-        # previous step's H2D DMA before rewriting the pinned staging
-        ev = entry.get("h2d_ev") if self.is_gpu else None
-        if ev is not None:
-            ev.synchronize()
-        entry["rows_pin"][:B] = torch.tensor(row_ids, dtype=torch.long)
-        entry["rows_pin"][B:] = self._pad_slot
-        entry["ids_pin"][:B] = torch.tensor([t for _s, t in plan],
-                                            dtype=torch.long)
-        entry["rows"].copy_(entry["rows_pin"], non_blocking=True)
-        entry["ids"].copy_(entry["ids_pin"], non_blocking=True)
-        if self.is_gpu:
-            if ev is None:
-                ev = entry["h2d_ev"] = torch.cuda.Event()
-            ev.record()
-        if entry["graph"] is not None:
-            entry["graph"].replay()
-            logits = entry["logits"][:B]
-        else:
-            logits = self._device_decode_fwd(entry["rows"], entry["ids"],
-                                             entry["inc"])[:B]
-        kvm.advance_many([s for s, _t in plan])
+        slots = self.kvm.decode_batch_prepare(seq_ids)
+        logits, _ = self._launch_decode(slots, [t for _s, t in plan],
+                                        ids_full=True)
+        self.kvm.advance_many(seq_ids)
         return logits
 
-    def _decode_async_worker(self, cmd: List[int]) -> None:
-        """Worker half of the speculative decode step (OP_DECODE_ASYNC).
-
-        Mirrors rank 0's phase-1 launch exactly: apply the prepended
-        rollbacks, prepare pages, feed carried-over rows from this rank's
-        OWN previous device sample (identical logits => identical sample),
-        replay the graph, sample on-device with the plan's per-row
-        (temp, top_p, effective-seed), advance. No host sync, no return
-        traffic — the worker runs ahead of its GPU."""
-        kvm = self.kvm
-        B = cmd[2]
-        nrb = cmd[3]
-        off = 4
-        rb = cmd[off:off + nrb]
-        off += nrb
-        if rb:
-            kvm.rollback_many([kvm.seq_of_slot(s) for s in rb])
-        rows_l: List[int] = []
-        toks_l: List[int] = []
-        idx_l: List[int] = []
-        seeds_l: List[int] = []
-        temps_l: List[float] = []
-        tops_l: List[float] = []
-        for i in range(B):
-            slot, tok, pidx, seed, tbits, pbits = cmd[off + 6 * i:off + 6 * i + 6]
-            rows_l.append(slot)
-            toks_l.append(tok if tok >= 0 else 0)
-            idx_l.append(pidx)
-            seeds_l.append(seed)
-            temps_l.append(_i2f(tbits))
-            tops_l.append(_i2f(pbits))
-        ext = self._recv_ext_tail(cmd, off + 6 * B, B)
-        seq_ids = [kvm.seq_of_slot(s) for s in rows_l]
-        kvm.decode_batch_prepare(seq_ids)  # same pages, deterministic
-        bucket = min(self._bucket(B), max(self.max_decode_batch, 1))
-        entry = self._get_graph(bucket)
+    def _launch_decode(self, slots: List[int], feed: List[int],
+                       prev_idx: Optional[List[int]] = None,
+                       prev_sampled: Optional[torch.Tensor] = None,
+                       ids_full: bool = False):
+        """The one staging + replay sequence of every rank and decode path.
+        Row i reads feed[i] or, where prev_idx[i] >= 0, that element of
+        prev_sampled (the previous step's device sample). Returns
+        (logits[:B], carried): carried is None or the (mask, gathered) of
+        that device-side feed, which the sampler's `pending` is built from.
+        ids_full keeps the synchronous path's copy of the pad rows' stale
+        ids: eager Mixtral at 65+ rows shapes its expert GEMMs by them."""
+        B = len(slots)
+        entry = self._get_graph(
+            min(self._bucket(B), max(self.max_decode_batch, 1)))
+        # the PREVIOUS step's non-blocking H2D copies read these pinned
+        # staging buffers; wait for that DMA before rewriting them (a
+        # torn read would feed wrong slots/tokens into the graph)
         ev = entry.get("h2d_ev") if self.is_gpu else None
         if ev is not None:
             ev.synchronize()
-        entry["rows_pin"][:B] = torch.tensor(rows_l, dtype=torch.long)
+        entry["rows_pin"][:B] = torch.tensor(slots, dtype=torch.long)
         entry["rows_pin"][B:] = self._pad_slot
         entry["rows"].copy_(entry["rows_pin"], non_blocking=True)
-        entry["ids_pin"][:B] = torch.tensor(toks_l, dtype=torch.long)
-        entry["ids"][:B].copy_(entry["ids_pin"][:B], non_blocking=True)
+        entry["ids_pin"][:B] = torch.tensor([max(t, 0) for t in feed],
+                                            dtype=torch.long)
+        n = None if ids_full else B
+        entry["ids"][:n].copy_(entry["ids_pin"][:n], non_blocking=True)
         if self.is_gpu:
             if ev is None:
                 ev = entry["h2d_ev"] = torch.cuda.Event()
             ev.record()
-        prev = self._spec_worker
-        pending = None
-        if prev is not None and any(x >= 0 for x in idx_l):
-            dev = self.device
-            gidx = torch.tensor([max(x, 0) for x in idx_l], dtype=torch.long,
-                                device=dev)
-            mask = torch.tensor([x >= 0 for x in idx_l], dtype=torch.bool,
-                                device=dev)
-            gathered = prev["sampled"].index_select(0, gidx)
-            entry["ids"][:B].copy_(torch.where(mask, gathered,
-                                               entry["ids"][:B]))
-            if ext is not None:
-                pending = torch.where(mask, gathered,
-                                      torch.full_like(gathered, -1))
+        carried = None
+        if prev_sampled is not None and any(x >= 0 for x in prev_idx):
+            gidx = torch.tensor([max(x, 0) for x in prev_idx],
+                                dtype=torch.long, device=self.device)
+            mask = torch.tensor([x >= 0 for x in prev_idx], dtype=torch.bool,
+                                device=self.device)
+            gathered = prev_sampled.index_select(0, gidx)
+            entry["ids"][:B].copy_(
+                torch.where(mask, gathered, entry["ids"][:B]))
+            carried = (mask, gathered)
         if entry["graph"] is not None:
             entry["graph"].replay()
-            logits = entry["logits"][:B]
-        else:
-            logits = self._device_decode_fwd(entry["rows"], entry["ids"],
-                                             entry["inc"])[:B]
-        sampled = self._sample_rows(logits, temps_l, tops_l, seeds_l, ext,
-                                    pending)
+            return entry["logits"][:B], carried
+        # eager fallback (capture failure / CPU emulation)
+        return self._device_decode_fwd(entry["rows"], entry["ids"],
+                                       entry["inc"])[:B], carried
+
+    def _run_async_plan(self, plan: AsyncDecodePlan,
+                        prev_sampled: Optional[torch.Tensor],
+                        seq_ids: Optional[List[str]] = None) -> torch.Tensor:
+        """One speculative decode step, the same on every rank: prepare
+        pages, launch (carried-over rows fed from this rank's OWN previous
+        device sample: identical logits => identical sample), sample
+        on-device by the plan's rows, advance. No host sync. Rank 0 passes
+        the seq_ids it has; a worker finds them by slot."""
+        kvm = self.kvm
+        if seq_ids is None:
+            seq_ids = [kvm.seq_of_slot(s) for s in plan.slots]
+        kvm.decode_batch_prepare(seq_ids)  # same pages, deterministic
+        logits, carried = self._launch_decode(plan.slots, plan.feed,
+                                              plan.prev_idx, prev_sampled)
+        pending = None
+        if carried is not None and plan.ext is not None:
+            # a carried-over row's newest token is not in its host lists
+            # yet: the sampler counts it from the device
+            mask, gathered = carried
+            pending = torch.where(mask, gathered,
+                                  torch.full_like(gathered, -1))
+        sampled = self._sample_rows(logits, plan.temps, plan.tops, plan.seeds,
+                                    plan.ext, pending)
         kvm.advance_many(seq_ids)
-        self.decode_tokens += B
-        self._spec_worker = {"sampled": sampled}
+        self.decode_tokens += len(seq_ids)
+        return sampled
 
-    def _send_ext_tail(self, vec: List[int], ext: List[Optional[Tuple]],
-                       tops_l: List[float]) -> None:
-        """Append the extended-sampling tail to an OP_DECODE_ASYNC vector:
-        n_ext, then per extended row [row, top_k, bits(min_p, rep, pres,
-        freq, top_p), n_edits, (tok, cnt, bias bits) * n_edits]. A tail too
-        long for the fixed plan buffer (long prompts under a repetition
-        penalty) travels ahead as a pickled command and the vector carries
-        n_ext = -1."""
-        rows = [i for i, sp in enumerate(ext) if sp is not None]
-        tail = [len(rows)]
-        for i in rows:
-            top_k, min_p, rep, pres, freq, edits = ext[i]
-            tail += [i, top_k, _f2i(min_p), _f2i(rep), _f2i(pres), _f2i(freq),
-                     _f2i(tops_l[i]), len(edits)]
-            for t, c, b in edits:
-                tail += [t, c, _f2i(b)]
-        if 1 + len(vec) + len(tail) <= par.PLAN_CAP:
-            vec += tail
-        else:
-            par.broadcast_obj(("ext_tail", self.name, tail))
-            vec.append(-1)
+    def _decode_async_worker(self, cmd: List[int]) -> None:
+        """Worker half of the speculative decode step: rank 0's plan after
+        its rollbacks. No return traffic — the worker runs ahead of its GPU."""
+        plan = wire.decode_async(cmd, self._take_ext_tail)
+        self.kvm.rollback_many([self.kvm.seq_of_slot(s)
+                                for s in plan.rollbacks])
+        self._spec_worker = self._run_async_plan(plan, self._spec_worker)
 
-    def _recv_ext_tail(self, cmd: List[int], off: int,
-                       B: int) -> Optional[List[Optional[Tuple]]]:
-        """Worker half of _send_ext_tail: per-row ext specs, or None when
-        the plan has no tail (no extended row in this step)."""
-        if off >= len(cmd):
-            return None
-        if cmd[off] < 0:
-            tail, self._ext_tail = self._ext_tail, None
-            off = 0
-        else:
-            tail = cmd
-        n_ext = tail[off]
-        off += 1
-        ext: List[Optional[Tuple]] = [None] * B
-        for _ in range(n_ext):
-            i, top_k, mp, rep, pres, freq, _tp, n = tail[off:off + 8]
-            off += 8
-            edits = [(tail[off + 3 * k], tail[off + 3 * k + 1],
-                      _i2f(tail[off + 3 * k + 2])) for k in range(n)]
-            off += 3 * n
-            ext[i] = (top_k, _i2f(mp), _i2f(rep), _i2f(pres), _i2f(freq),
-                      edits)
-        return ext
+    def _take_ext_tail(self) -> List[int]:
+        tail, self._ext_tail = self._ext_tail, None
+        return tail
 
     def _finish_or_run(self, r: GenRequest, tok: int):
         """Called with lock held, after appending tok."""
@@ -2093,29 +1969,26 @@ class LLMEngine:
         while True:
             cmd = par.recv_cmd()
             if isinstance(cmd, list):  # int-vector fast path
-                op = cmd[0]
-                if op == OP_DECODE:
-                    inst = self._instances[self._instance_order[cmd[1]]]
-                    B = cmd[2]
-                    kvm = inst.kvm
-                    plan = [(kvm.seq_of_slot(s), t)
-                            for s, t in zip(cmd[3:3 + B], cmd[3 + B:3 + 2 * B])]
-                    inst._decode_exec(plan)
-                elif op == OP_DECODE_ASYNC:
-                    inst = self._instances[self._instance_order[cmd[1]]]
-                    inst._decode_async_worker(cmd)
-                elif op == OP_ROLLBACK:
-                    inst = self._instances[self._instance_order[cmd[1]]]
-                    n = cmd[2]
-                    inst.kvm.rollback_many(
-                        [inst.kvm.seq_of_slot(s) for s in cmd[3:3 + n]])
-                elif op == OP_BARRIER:
+                op, model_idx = wire.header(cmd)
+                if op == OP_BARRIER:
                     # timing fence (bench.py --tp): drain this rank's
                     # stream, then rendezvous so rank 0's clock bounds
                     # every rank
                     if self.device.startswith("cuda"):
                         torch.cuda.synchronize()
                     par.barrier()
+                    continue
+                inst = self._instances[self._instance_order[model_idx]]
+                kvm = inst.kvm
+                if op == OP_DECODE:
+                    inst._decode_exec(
+                        [(kvm.seq_of_slot(s), t)
+                         for s, t in zip(*wire.decode_sync(cmd))])
+                elif op == OP_DECODE_ASYNC:
+                    inst._decode_async_worker(cmd)
+                elif op == OP_ROLLBACK:
+                    kvm.rollback_many([kvm.seq_of_slot(s)
+                                       for s in wire.decode_rollback(cmd)])
                 continue
             op = cmd[0]
             if op == "shutdown":

@@ -204,38 +204,44 @@ def test_tp2_async_decode_token_exact_with_sampling_controls(tmp_path):
 def test_plan_tail_round_trip_and_overflow():
     """The tail decodes to the specs it encoded; one too long for the plan
     vector is announced with n_ext = -1 and read from the stashed list."""
-    from agentainer_amd.engine import llm
+    from agentainer_amd.engine import llm, plan
+
+    def rows(tops, ext):
+        z = [0] * len(tops)
+        return plan.AsyncDecodePlan(slots=z, feed=z, prev_idx=z, seeds=z,
+                                    temps=[0.0] * len(tops), tops=tops,
+                                    ext=ext)
 
     inst = llm.ModelInstance.__new__(llm.ModelInstance)
-    inst.name = "m"
+    inst._ext_tail = None
     ext = [None,
            (40, 0.05, 1.3, -0.5, 0.25, [(0, 1, 0.0), (7, 5, -100.0)]),
            None,
            (0, 0.0, 1.0, 0.0, 0.0, [(511, 0, 2.5)])]
-    vec = [llm.OP_DECODE_ASYNC, 0, 4, 0] + [0] * 24
-    n0 = len(vec)
-    inst._send_ext_tail(vec, ext, [1.0, 0.9, 1.0, 1.0])
+    vec = plan.encode_async(0, "m", rows([1.0, 0.9, 1.0, 1.0], ext))
+    assert vec[:4] == [llm.OP_DECODE_ASYNC, 0, 4, 0]
+    n0 = 4 + 6 * 4
     assert vec[n0] == 2
-    got = inst._recv_ext_tail(vec, n0, 4)
+    got = plan.decode_async(vec, inst._take_ext_tail).ext
     f32 = lambda x: torch.tensor(x, dtype=torch.float32).item()
     want = [None if sp is None else
             (sp[0], f32(sp[1]), f32(sp[2]), f32(sp[3]), f32(sp[4]), sp[5])
             for sp in ext]
     assert got == want
-    assert inst._recv_ext_tail(vec[:n0], n0, 4) is None  # today's vector
+    # today's vector
+    assert plan.decode_async(vec[:n0], inst._take_ext_tail).ext is None
     # overflow: the tail rides a pickled command instead
     sent = []
     big = [(1, 0.0, 1.1, 0.0, 0.0, [(t, 1, 0.0) for t in range(9000)])]
     real = llm.par.broadcast_obj
     llm.par.broadcast_obj = sent.append
     try:
-        vec = [llm.OP_DECODE_ASYNC, 0, 1, 0] + [0] * 6
-        inst._send_ext_tail(vec, big, [1.0])
+        vec = plan.encode_async(0, "m", rows([1.0], big))
     finally:
         llm.par.broadcast_obj = real
     assert vec[-1] == -1 and len(vec) == 11 and sent[0][0] == "ext_tail"
     inst._ext_tail = sent[0][2]
-    got = inst._recv_ext_tail(vec, 10, 1)
+    got = plan.decode_async(vec, inst._take_ext_tail).ext
     assert got[0][0] == 1 and got[0][5] == big[0][5]
     assert inst._ext_tail is None
 
