@@ -253,15 +253,9 @@ class ModelInstance:
                       else 0.5 if (fp8 or dq == "fp8") else 1.0)
             free, total = torch.cuda.mem_get_info()
             if param_bytes * (1.0 + factor) < 0.75 * total:
-                import inspect
-                sig = inspect.signature(self.model.pack_decode_weights)
-                if "expert_fp8" in sig.parameters:
-                    self.model.pack_decode_weights(expert_fp8=fp8,
-                                                   expert_fp4=fp4)
-                elif "dense_quant" in sig.parameters:
-                    self.model.pack_decode_weights(dense_quant=dq)
-                else:
-                    self.model.pack_decode_weights()
+                self.model.pack_decode_weights(
+                    dense_quant=dq,
+                    expert_quant="mxfp4" if fp4 else "fp8" if fp8 else "")
         page_size = int(engine_cfg.get("kv_page_size", 16))
         kv_dtype_s = str(engine_cfg.get("kv_dtype", "bf16"))
         if kv_dtype_s in ("fp8", "fp8_e4m3", "e4m3"):

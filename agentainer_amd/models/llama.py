@@ -4,7 +4,10 @@ The model is written for the paged multi-tenant engine, not as a generic
 HF module: every hot op dispatches to the gfx950 HIP kernels
 (agentainer_amd.ops), plain GEMMs go to hipBLASLt via F.linear, and the
 forward takes paged-KV attention metadata (prefill: varlen packed rows;
-decode: one row per sequence). Weights are bf16, random-init by default
+decode: one row per sequence). Each projection weight sits beside an
+ops.Projection that owns its packed or quantized decode form and picks
+the GEMM (qkv_lin, o_lin, gate_up_lin, down_lin, lm_head_lin). Weights
+are bf16, random-init by default
 (BASELINE.json: synthetic prompts / random-init weights; no network for
 checkpoints) with a safetensors loader for real weights.
 
@@ -90,11 +93,8 @@ class LlamaAttention(torch.nn.Module):
         self.qkv_bias = (torch.nn.Parameter(
             torch.zeros(q_out + 2 * kv_out, dtype=torch.bfloat16))
             if cfg.qkv_bias else None)
-        self.qkv_packed = None
-        self.o_packed = None
-        # opt-in quantized decode weights ("turbo": engine.dense_quant)
-        self.qkv_q = None
-        self.o_q = None
+        self.qkv_lin = ops.Projection(self.qkv_proj)
+        self.o_lin = ops.Projection(self.o_proj)
 
     def forward(self, h, k_cache, v_cache, md: AttnMetadata, cos_sin,
                 tp_group=None, defer_reduce: bool = False, lora=None,
@@ -106,10 +106,7 @@ class LlamaAttention(torch.nn.Module):
         lora: models.lora.LoraContext or None; each projection's adapter
         delta is added to its GEMM output in place."""
         T = h.size(0)
-        if self.qkv_q is not None and T <= 64 and h.is_cuda:
-            qkv = ops.linear_quant(h, self.qkv_q)
-        else:
-            qkv = ops.linear(h, self.qkv_proj, self.qkv_packed)
+        qkv = self.qkv_lin(h)
         if self.qkv_bias is not None:
             qkv = qkv + self.qkv_bias
         if lora is not None:
@@ -133,13 +130,8 @@ class LlamaAttention(torch.nn.Module):
         else:
             ops.paged_decode_attention(out, q, k_cache, v_cache, md.page_table,
                                        md.seq_lens, self.scale)
-        if self.o_q is not None and T <= 64 and h.is_cuda:
-            o = ops.linear_quant(out.view(T, q_sz), self.o_q)
-        elif defer_reduce and tp_group is None and lora is None:
-            o = ops.linear_partial(out.view(T, q_sz), self.o_proj,
-                                   self.o_packed)
-        else:
-            o = ops.linear(out.view(T, q_sz), self.o_proj, self.o_packed)
+        o = self.o_lin(out.view(T, q_sz), defer=(
+            defer_reduce and tp_group is None and lora is None))
         if lora is not None:
             lora.apply(layer_idx, "o", o, out.view(T, q_sz))
         if tp_group is not None:
@@ -156,31 +148,21 @@ class LlamaMLP(torch.nn.Module):
         self.down = torch.nn.Parameter(
             torch.empty(cfg.hidden_size, inter, dtype=torch.bfloat16))
         self.inter = inter
-        self.gate_up_packed = None
-        self.down_packed = None
-        self.gate_up_q = None
-        self.down_q = None
+        self.gate_up_lin = ops.Projection(self.gate_up)
+        self.down_lin = ops.Projection(self.down)
 
     def forward(self, h, tp_group=None, defer_reduce: bool = False,
                 lora=None, layer_idx: int = 0):
         # defer_reduce, lora: as in LlamaAttention.forward, for the down-proj
-        turbo = self.gate_up_q is not None and h.size(0) <= 64 and h.is_cuda
-        if turbo:
-            gu = ops.linear_quant(h, self.gate_up_q)
-        else:
-            gu = ops.linear(h, self.gate_up, self.gate_up_packed)
+        gu = self.gate_up_lin(h)
         if lora is not None:
             lora.apply(layer_idx, "gate_up", gu, h)
         gate, up = gu[:, :self.inter], gu[:, self.inter:]
         act = torch.empty(gu.size(0), self.inter, dtype=gu.dtype,
                           device=gu.device)
         ops.silu_mul(act, gate, up)
-        if turbo:
-            out = ops.linear_quant(act, self.down_q)
-        elif defer_reduce and tp_group is None and lora is None:
-            out = ops.linear_partial(act, self.down, self.down_packed)
-        else:
-            out = ops.linear(act, self.down, self.down_packed)
+        out = self.down_lin(act, defer=(
+            defer_reduce and tp_group is None and lora is None))
         if lora is not None:
             lora.apply(layer_idx, "down", out, act)
         if tp_group is not None:
@@ -241,6 +223,7 @@ class LlamaForCausalLM(torch.nn.Module):
             else:
                 self.lm_head = torch.nn.Parameter(
                     torch.empty(cfg.vocab_size, cfg.hidden_size, dtype=torch.bfloat16))
+        self.lm_head_lin = ops.Projection(self.lm_head)
         self.register_buffer(
             "cos_sin",
             ops.make_cos_sin_table(cfg.max_position, cfg.head_dim, cfg.rope_theta,
@@ -277,46 +260,25 @@ class LlamaForCausalLM(torch.nn.Module):
         ops.fused_add_rmsnorm(final, hidden, residual, self.final_ln, self.cfg.norm_eps)
         if last_rows is not None:
             final = final[last_rows]
-        return ops.linear(final, self.lm_head,
-                          getattr(self, 'lm_head_packed', None))  # bf16
+        return self.lm_head_lin(final)  # bf16
 
     @torch.no_grad()
-    def pack_decode_weights(self, dense_quant: str = ""):
+    def pack_decode_weights(self, dense_quant: str = "",
+                            expert_quant: str = ""):
         """Pre-shuffle every projection weight into the fragment-linear
-        layout the skinny decode GEMM streams (ops.pack_weight). Keeps the
-        natural-layout Parameters for the prefill hipBLASLt path — the
+        layout the skinny decode GEMM streams (ops.Projection.pack). Keeps
+        the natural-layout Parameters for the prefill hipBLASLt path — the
         packed copies double weight memory, well inside 288 GB HBM3E.
 
         dense_quant: "" (bf16, the default/headline dtype), "fp8"
         (per-channel e4m3), or "mxfp4" (e2m1 + e8m0 block-32 scales) —
-        opt-in reduced-precision DECODE projections (prefill stays bf16)."""
+        opt-in reduced-precision DECODE projections (prefill and the
+        lm_head stay bf16). expert_quant: unused (no experts)."""
         for layer in self.layers:
-            if dense_quant == "mxfp4":
-                for mod_, wname, qname in (
-                        (layer.attn, "qkv_proj", "qkv_q"),
-                        (layer.attn, "o_proj", "o_q"),
-                        (layer.mlp, "gate_up", "gate_up_q"),
-                        (layer.mlp, "down", "down_q")):
-                    w = getattr(mod_, wname).data
-                    p, sc = ops.quantize_weight_mxfp4(w)
-                    setattr(mod_, qname, ("mxfp4", p, sc, w.size(0)))
-            elif dense_quant == "fp8":
-                for mod_, wname, qname in (
-                        (layer.attn, "qkv_proj", "qkv_q"),
-                        (layer.attn, "o_proj", "o_q"),
-                        (layer.mlp, "gate_up", "gate_up_q"),
-                        (layer.mlp, "down", "down_q")):
-                    w = getattr(mod_, wname).data
-                    p, sw = ops.quantize_weight_fp8(w)
-                    setattr(mod_, qname, ("fp8", p, sw, w.size(0)))
-            else:
-                layer.attn.qkv_packed = ops.pack_weight(layer.attn.qkv_proj.data)
-                layer.attn.o_packed = ops.pack_weight(layer.attn.o_proj.data)
-                layer.mlp.gate_up_packed = ops.pack_weight(layer.mlp.gate_up.data)
-                layer.mlp.down_packed = ops.pack_weight(layer.mlp.down.data)
-        self.lm_head_packed = ops.pack_weight(
-            self.lm_head.data if isinstance(self.lm_head, torch.nn.Parameter)
-            else self.lm_head)
+            for proj in (layer.attn.qkv_lin, layer.attn.o_lin,
+                         layer.mlp.gate_up_lin, layer.mlp.down_lin):
+                proj.pack(dense_quant)
+        self.lm_head_lin.pack()
 
     @torch.no_grad()
     def load_safetensors(self, path: str):

@@ -32,12 +32,14 @@ MoE execution model, chosen for the MI355X serving regime:
     (v_mfma_scale_f32_16x16x128_f8f6f4, operand maps probed in
     tools/mx_probe.py) — QUARTER the expert bytes; measured 17.1 req/s
     vs 14.2 bf16 at the config-5 bench.
+  * Each expert GEMM is an ops.Projection holding whichever of those
+    decode forms was packed; it alone decides which GEMM a batch takes.
 """
 
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict
 
 import torch
 import torch.nn.functional as F
@@ -74,14 +76,9 @@ class MixtralMoE(torch.nn.Module):
                                            dtype=torch.bfloat16))
             for _ in range(self.n_local)])
         self.inter = inter
-        self.gate_up_packed: List[Optional[torch.Tensor]] = [None] * self.n_local
-        self.down_packed: List[Optional[torch.Tensor]] = [None] * self.n_local
-        # fp8 expert path (config 5): (packed bytes, scales) per expert
-        self.gate_up_fp8: List[Optional[tuple]] = [None] * self.n_local
-        self.down_fp8: List[Optional[tuple]] = [None] * self.n_local
-        # MXFP4 expert path (block-scaled fp4 MFMA): quarter the bytes
-        self.gate_up_fp4: List[Optional[tuple]] = [None] * self.n_local
-        self.down_fp4: List[Optional[tuple]] = [None] * self.n_local
+        # decode forms per expert: bf16-packed, fp8 (config 5) or MXFP4
+        self.gate_up_lin = [ops.Projection(w) for w in self.gate_up]
+        self.down_lin = [ops.Projection(w) for w in self.down]
 
     # batches at least this big use token-shuffle all-to-all EP by default
     A2A_MIN_TOKENS = 128
@@ -120,34 +117,28 @@ class MixtralMoE(torch.nn.Module):
         weight = torch.zeros_like(probs)
         weight.scatter_(1, topi, topv)
         out = torch.zeros_like(h, dtype=torch.float32)
-        use_fp8 = (h.is_cuda and T <= 64 and self.gate_up_fp8[0] is not None)
-        use_fp4 = (h.is_cuda and T <= 64 and self.gate_up_fp4[0] is not None)
         for i in range(self.n_local):
-            e = self.e0 + i
-            if use_fp4:
-                wp, sw = self.gate_up_fp4[i]
-                gu = ops.linear_mxfp4(h, wp, sw, 2 * self.inter)
-            elif use_fp8:
-                wp, sw = self.gate_up_fp8[i]
-                gu = ops.linear_fp8(h, wp, sw, 2 * self.inter)
-            else:
-                gu = ops.linear(h, self.gate_up[i], self.gate_up_packed[i])
-            gate, up = gu[:, :self.inter], gu[:, self.inter:]
-            act = torch.empty(T, self.inter, dtype=gu.dtype, device=gu.device)
-            ops.silu_mul(act, gate, up)
-            if use_fp4:
-                wp, sw = self.down_fp4[i]
-                eo = ops.linear_mxfp4(act, wp, sw, h.size(1))
-            elif use_fp8:
-                wp, sw = self.down_fp8[i]
-                eo = ops.linear_fp8(act, wp, sw, h.size(1))
-            else:
-                eo = ops.linear(act, self.down[i], self.down_packed[i])
-            out += weight[:, e].unsqueeze(1) * eo.float()
+            eo = self._swiglu(h, self.gate_up_lin[i], self.down_lin[i])
+            out += weight[:, self.e0 + i].unsqueeze(1) * eo.float()
         out = out.to(h.dtype)
         if ep_group is not None:
             torch.distributed.all_reduce(out, group=ep_group)
         return out
+
+    def _swiglu(self, x: torch.Tensor, gate_up, down) -> torch.Tensor:
+        """One SwiGLU expert over x; gate_up and down are ops.Projection."""
+        gu = gate_up(x)
+        gate, up = gu[:, :self.inter], gu[:, self.inter:]
+        act = torch.empty(x.size(0), self.inter, dtype=gu.dtype,
+                          device=gu.device)
+        ops.silu_mul(act, gate, up)
+        return down(act)
+
+    def _natural(self, i: int):
+        # expert i for the gather routes below: the natural-layout weights
+        # at any M, never the packed or quantized decode form (with
+        # ep_mode "a2a" a decode-sized batch gets here too)
+        return ops.Projection(self.gate_up[i]), ops.Projection(self.down[i])
 
     def _experts_sparse(self, h: torch.Tensor, topi: torch.Tensor,
                         topv: torch.Tensor) -> torch.Tensor:
@@ -166,12 +157,7 @@ class MixtralMoE(torch.nn.Module):
                 continue
             w = (topv * hit.float()).sum(dim=-1)[rows]  # [n] routing weight
             x = h.index_select(0, rows)
-            gu = ops.linear(x, self.gate_up[i], None)
-            gate, up = gu[:, :self.inter], gu[:, self.inter:]
-            act = torch.empty(x.size(0), self.inter, dtype=gu.dtype,
-                              device=gu.device)
-            ops.silu_mul(act, gate, up)
-            eo = ops.linear(act, self.down[i], None)
+            eo = self._swiglu(x, *self._natural(i))
             out.index_add_(0, rows, w.unsqueeze(1).float() * eo.float())
         return out.to(h.dtype)
 
@@ -247,13 +233,7 @@ class MixtralMoE(torch.nn.Module):
                 sel = (le == i).nonzero(as_tuple=True)[0]
                 if sel.numel() == 0:
                     continue
-                xi = xd[sel]
-                gu = ops.linear(xi, self.gate_up[i], None)
-                gate, up = gu[:, :self.inter], gu[:, self.inter:]
-                act = torch.empty(xi.shape[0], self.inter, dtype=gu.dtype,
-                                  device=gu.device)
-                ops.silu_mul(act, gate, up)
-                eo = ops.linear(act, self.down[i], None)
+                eo = self._swiglu(xd[sel], *self._natural(i))
                 yd[sel] = md[sel, 2].unsqueeze(1) * eo.float()
             results.append(yd.to(h.dtype).contiguous())
         returned = self._exchange(results, ep_group)
@@ -324,6 +304,7 @@ class MixtralForCausalLM(torch.nn.Module):
                 torch.empty(cfg.hidden_size, dtype=torch.bfloat16))
             self.lm_head = torch.nn.Parameter(
                 torch.empty(cfg.vocab_size, cfg.hidden_size, dtype=torch.bfloat16))
+        self.lm_head_lin = ops.Projection(self.lm_head)
         self.register_buffer(
             "cos_sin",
             ops.make_cos_sin_table(cfg.max_position, cfg.head_dim,
@@ -342,28 +323,16 @@ class MixtralForCausalLM(torch.nn.Module):
                 p.fill_(1.0)
 
     @torch.no_grad()
-    def pack_decode_weights(self, expert_fp8: bool = False,
-                            expert_fp4: bool = False):
+    def pack_decode_weights(self, dense_quant: str = "",
+                            expert_quant: str = ""):
+        """expert_quant: "" (bf16-packed), "fp8" or "mxfp4" decode experts.
+        dense_quant: unused — attention and the lm_head stay bf16-packed."""
         for layer in self.layers:
-            layer.attn.qkv_packed = ops.pack_weight(layer.attn.qkv_proj.data)
-            layer.attn.o_packed = ops.pack_weight(layer.attn.o_proj.data)
-            for i in range(layer.moe.n_local):
-                if expert_fp4:
-                    layer.moe.gate_up_fp4[i] = ops.quantize_weight_mxfp4(
-                        layer.moe.gate_up[i].data)
-                    layer.moe.down_fp4[i] = ops.quantize_weight_mxfp4(
-                        layer.moe.down[i].data)
-                elif expert_fp8:
-                    layer.moe.gate_up_fp8[i] = ops.quantize_weight_fp8(
-                        layer.moe.gate_up[i].data)
-                    layer.moe.down_fp8[i] = ops.quantize_weight_fp8(
-                        layer.moe.down[i].data)
-                else:
-                    layer.moe.gate_up_packed[i] = ops.pack_weight(
-                        layer.moe.gate_up[i].data)
-                    layer.moe.down_packed[i] = ops.pack_weight(
-                        layer.moe.down[i].data)
-        self.lm_head_packed = ops.pack_weight(self.lm_head.data)
+            layer.attn.qkv_lin.pack()
+            layer.attn.o_lin.pack()
+            for proj in layer.moe.gate_up_lin + layer.moe.down_lin:
+                proj.pack(expert_quant)
+        self.lm_head_lin.pack()
 
     @torch.no_grad()
     def forward(self, input_ids, md: AttnMetadata, kv_caches,
@@ -379,8 +348,7 @@ class MixtralForCausalLM(torch.nn.Module):
                               self.cfg.norm_eps)
         if last_rows is not None:
             final = final[last_rows]
-        return ops.linear(final, self.lm_head,
-                          getattr(self, "lm_head_packed", None))
+        return self.lm_head_lin(final)
 
 
 MIXTRAL_CONFIGS: Dict[str, MixtralConfig] = {

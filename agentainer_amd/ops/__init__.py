@@ -269,14 +269,20 @@ def _skinny_split(ntiles: int, K: int) -> int:
     return split
 
 
+def _fragment_linear(w: torch.Tensor) -> torch.Tensor:
+    # [N, K] -> flat packed[n_tile][k_chunk][lane][8], 2- or 1-byte elements
+    N, K = w.shape
+    return (w.view(N // 16, 16, K // 32, 4, 8)
+            .permute(0, 2, 3, 1, 4).contiguous().view(-1))
+
+
 def pack_weight(w: torch.Tensor) -> torch.Tensor:
     """Shuffle a static [N, K] weight into MFMA-fragment-linear layout
     packed[n_tile][k_chunk][lane][8] so the skinny GEMM's weight stream is
     contiguous per wave. Done once at model load; flat [N*K] result."""
     N, K = w.shape
     assert N % 16 == 0 and K % 32 == 0
-    p = w.view(N // 16, 16, K // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous()
-    return p.view(-1)
+    return _fragment_linear(w)
 
 
 class _Workspace:
@@ -384,16 +390,13 @@ def quantize_weight_fp8(w: torch.Tensor):
     """Offline per-output-channel OCP e4m3 quantization of a [N, K] weight:
     returns (fragment-linear packed bytes, f32 scales[N]). Serves the fp8
     MFMA expert decode GEMM (BASELINE config 5)."""
-    N, K = w.shape
     sw = w.float().abs().amax(dim=1).clamp(min=1e-8) / 448.0
     scaled = (w.float() / sw[:, None]).clamp(-448.0, 448.0)
     try:
         w8 = scaled.to(torch.float8_e4m3fn).view(torch.uint8)
     except (RuntimeError, TypeError):
         w8 = scaled.cpu().to(torch.float8_e4m3fn).view(torch.uint8).to(w.device)
-    packed = (w8.view(N // 16, 16, K // 32, 4, 8)
-              .permute(0, 2, 3, 1, 4).contiguous().view(-1))
-    return packed, sw.float().contiguous()
+    return _fragment_linear(w8), sw.float().contiguous()
 
 
 def linear_fp8(x: torch.Tensor, w_packed: torch.Tensor, sw: torch.Tensor,
@@ -501,6 +504,45 @@ def linear_quant(x: torch.Tensor, qt) -> torch.Tensor:
     if kind == "mxfp4":
         return linear_mxfp4(x, packed, scales, N)
     return linear_fp8(x, packed, scales, N)
+
+
+class Projection:
+    """A static [N, K] projection weight (kept by reference) with at most
+    one decode form, and the one rule for which GEMM it takes: pack()
+    builds the bf16 fragment-linear copy, pack("fp8" | "mxfp4") the
+    quantized form instead."""
+    __slots__ = ("w", "packed", "quant")
+
+    def __init__(self, w: torch.Tensor):
+        self.w = w
+        self.packed = None  # pack_weight(w)
+        self.quant = None   # linear_quant's (kind, packed, scales, N)
+
+    @property
+    def kind(self) -> Optional[str]:
+        if self.quant is not None:
+            return self.quant[0]
+        return "bf16" if self.packed is not None else None
+
+    @torch.no_grad()
+    def pack(self, quant: str = "") -> "Projection":
+        self.packed = self.quant = None
+        if quant == "":
+            self.packed = pack_weight(self.w.data)
+        else:
+            quantize = {"fp8": quantize_weight_fp8,
+                        "mxfp4": quantize_weight_mxfp4}[quant]
+            self.quant = (quant, *quantize(self.w.data), self.w.size(0))
+        return self
+
+    def __call__(self, x: torch.Tensor, defer: bool = False):
+        """x[M,K] @ w^T. The quantized form serves decode-shaped GPU
+        batches and wins over defer; everything else is linear(), or
+        with defer linear_partial() (the result may be a SplitKPartial)."""
+        if self.quant is not None and x.size(0) <= 64 and x.is_cuda:
+            return linear_quant(x, self.quant)
+        return _linear(x, self.w, self.packed,
+                       defer and not SPLITK_DEFER_DISABLED)
 
 
 def lora_shrink(v, x, A, ids):

@@ -337,8 +337,7 @@ def test_dense_quant_turbo_generation(tmp_path):
             b = manager.deploy(name="t2", model="tiny-llama")
             manager.start(b.id)
             inst = engine._instances["tiny-llama"]
-            assert inst.model.layers[0].attn.qkv_q is not None
-            assert inst.model.layers[0].attn.qkv_q[0] == dq
+            assert inst.model.layers[0].attn.qkv_lin.kind == dq
             prompt = list(range(3, 40))
             o1 = _gen(engine, manager, a, prompt)
             o2 = _gen(engine, manager, b, prompt)

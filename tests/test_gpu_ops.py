@@ -558,7 +558,7 @@ def test_mixtral_fp4_experts_generate():
         a = manager.deploy(name="mx4", model="tiny-mixtral")
         manager.start(a.id)
         inst = engine._instances["tiny-mixtral"]
-        assert inst.model.layers[0].moe.gate_up_fp4[0] is not None
+        assert inst.model.layers[0].moe.gate_up_lin[0].kind == "mxfp4"
         out = _gen(engine, manager, a, list(range(3, 40)), max_new=6)
         assert len(out) == 6
     finally:
