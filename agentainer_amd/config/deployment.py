@@ -61,7 +61,8 @@ class AgentSpec:
     system_prompt: str = ""
     lora: str = ""               # LoRA adapter directory; "" = base model
     # temperature/top_p/seed/max_tokens, and the extended controls top_k/
-    # min_p/repetition_penalty/presence_penalty/frequency_penalty/logit_bias
+    # min_p/repetition_penalty/presence_penalty/frequency_penalty/logit_bias,
+    # and logprobs/top_logprobs
     # (defaults here, overridable per request; docs/API_ENDPOINTS.md)
     sampling: Dict[str, Any] = field(default_factory=dict)
     dependencies: List[str] = field(default_factory=list)

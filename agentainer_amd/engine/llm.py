@@ -91,6 +91,12 @@ class GenRequest:
     # generated (kept by add_token, wherever `generated` grows)
     prompt_set: Optional[frozenset] = None
     gen_counts: Dict[int, int] = field(default_factory=dict)
+    # logprobs of the model's own distribution (ops.token_logprobs): with
+    # `logprobs` on, token_logprobs holds one entry per generated token,
+    # {"token", "logprob", "top": [{"token", "logprob"}] * top_logprobs}
+    logprobs: bool = False
+    top_logprobs: int = 0
+    token_logprobs: List[Dict[str, Any]] = field(default_factory=list)
 
     # whether any control above is on; fixed at construction so that the
     # per-step routing check costs one attribute read per row
@@ -104,9 +110,15 @@ class GenRequest:
             or self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
             or self.frequency_penalty != 0.0 or self.logit_bias)
 
-    def add_token(self, tok: int) -> None:
+    def add_token(self, tok: int, lp: Optional[Tuple] = None) -> None:
+        """lp: a requesting row's (logprob, [(token, logprob), ...]) from
+        ModelInstance._fetch_logprobs."""
         self.generated.append(tok)
         self.gen_counts[tok] = self.gen_counts.get(tok, 0) + 1
+        if self.logprobs:
+            self.token_logprobs.append({
+                "token": tok, "logprob": lp[0],
+                "top": [{"token": t, "logprob": p} for t, p in lp[1]]})
 
     def ext_spec(self) -> Optional[Tuple]:
         """(top_k, min_p, rep, pres, freq, edits) for an extended request,
@@ -129,12 +141,14 @@ class GenRequest:
 
 SAMPLING_TOP_K_MAX = 1024
 SAMPLING_MAX_BIASES = 300
+SAMPLING_TOP_LOGPROBS_MAX = 20  # ops.token_logprobs' K
 
 
 def parse_sampling_controls(sampling: Dict[str, Any], vocab: int) -> Dict[str, Any]:
     """Validate the extended sampling keys of a merged sampling dict and
-    return them as GenRequest keyword arguments. Raises ValueError on an
-    ill-typed or out-of-range value."""
+    return them as GenRequest keyword arguments (`logprobs` and
+    `top_logprobs` only when logprobs are asked for). Raises ValueError on
+    an ill-typed or out-of-range value."""
     def num(key, default, lo, hi, lo_open=False):
         v = sampling.get(key, default)
         if isinstance(v, bool) or not isinstance(v, (int, float)):
@@ -173,7 +187,19 @@ def parse_sampling_controls(sampling: Dict[str, Any], vocab: int) -> Dict[str, A
         if t in bias:
             raise ValueError(f"sampling.logit_bias token id {t} given twice")
         bias[t] = float(v)
-    return dict(
+    want_lp = sampling.get("logprobs", False)
+    if not isinstance(want_lp, bool):
+        raise ValueError(f"sampling.logprobs must be a boolean, got {want_lp!r}")
+    top_lp = sampling.get("top_logprobs", 0)
+    if isinstance(top_lp, bool) or not isinstance(top_lp, int):
+        raise ValueError(
+            f"sampling.top_logprobs must be an integer, got {top_lp!r}")
+    if not 0 <= top_lp <= SAMPLING_TOP_LOGPROBS_MAX:
+        raise ValueError(f"sampling.top_logprobs={top_lp} out of range "
+                         f"[0, {SAMPLING_TOP_LOGPROBS_MAX}]")
+    if top_lp and not want_lp:
+        raise ValueError("sampling.top_logprobs requires sampling.logprobs")
+    controls = dict(
         top_k=top_k,
         min_p=num("min_p", 0.0, 0.0, 1.0),
         repetition_penalty=num("repetition_penalty", 1.0, 0.0,
@@ -182,6 +208,9 @@ def parse_sampling_controls(sampling: Dict[str, Any], vocab: int) -> Dict[str, A
         frequency_penalty=num("frequency_penalty", 0.0, -2.0, 2.0),
         logit_bias=bias,
     )
+    if want_lp:
+        controls.update(logprobs=True, top_logprobs=top_lp)
+    return controls
 
 
 @dataclass
@@ -585,10 +614,14 @@ class ModelInstance:
                 # their own identical logits (no return traffic)
                 par.send_ints(wire.encode_async(self._model_idx, self.name,
                                                 plan))
-            sampled = self._run_async_plan(
-                plan, prev["sampled"] if prev else None, seq_ids)
+            sampled, lp = self._run_async_plan(
+                plan, prev["sampled"] if prev else None, seq_ids,
+                lp_reqs=batch)
             self.occupancy_acc += len(batch) / max(1, self.max_decode_batch)
-            launched = {"reqs": batch, "sampled": sampled, "invalid": set()}
+            # lp: the logprobs kernel's own output tensors (or None), not
+            # the graph's logits buffer that the next replay overwrites
+            launched = {"reqs": batch, "sampled": sampled, "invalid": set(),
+                        "logprobs": lp}
         t0 = self._phase_mark("p1_launch_ms", t0)
         self._spec = launched
 
@@ -661,6 +694,7 @@ class ModelInstance:
         if prev is None:
             return
         toks = prev["sampled"].tolist()
+        lps = self._fetch_logprobs(prev["logprobs"])
         rollback_seqs = []
         with self._lock:
             lpos = ({id(r): i for i, r in enumerate(launched["reqs"])}
@@ -670,7 +704,7 @@ class ModelInstance:
                     # invalidated row, or the request died (detach) mid-flight
                     continue
                 t = int(toks[i])
-                r.add_token(t)
+                r.add_token(t, lps.get(i))
                 self._finish_or_run(r, t)
                 if r.done.is_set():
                     # the just-launched step speculatively appended a token
@@ -767,6 +801,47 @@ class ModelInstance:
 
     def _sample(self, logits: torch.Tensor, reqs: List[GenRequest]) -> List[int]:
         return self._sample_device(logits, reqs).tolist()
+
+    def _sample_lp(self, logits: torch.Tensor, reqs: List[GenRequest]):
+        """_sample, and each requesting row's logprobs as _fetch_logprobs
+        returns them. Without such a row this is _sample alone."""
+        if not any(r.logprobs for r in reqs):
+            return self._sample(logits, reqs), {}
+        sampled = self._sample_device(logits, reqs)
+        lp = self._launch_logprobs(logits, reqs, sampled)
+        return sampled.tolist(), self._fetch_logprobs(lp)
+
+    def _launch_logprobs(self, logits: torch.Tensor, reqs: List[GenRequest],
+                         sampled: torch.Tensor) -> Optional[Tuple]:
+        """ops.token_logprobs right behind the sampler, in its stream, over
+        the rows that ask, with K the largest top_logprobs among them.
+        Returns None (nothing launched or built) when no row asks, else
+        (rows, their top_logprobs, chosen_lp, top_id, top_lp) with the
+        three outputs still on the device. Rank 0 only: the kernel holds
+        no collective and only rank 0 answers clients."""
+        rows = [i for i, r in enumerate(reqs) if r.logprobs]
+        if not rows:
+            return None
+        tops = [reqs[i].top_logprobs for i in rows]
+        rows_t = torch.tensor(rows, dtype=torch.int32).to(
+            logits.device, non_blocking=True)
+        lb = logits.to(torch.bfloat16).contiguous()  # as the samplers read it
+        return (rows, tops, *ops.token_logprobs(lb, rows_t, sampled, max(tops)))
+
+    @staticmethod
+    def _fetch_logprobs(lp: Optional[Tuple]) -> Dict[int, Tuple]:
+        """Bring a _launch_logprobs result to the host (a sync point, taken
+        beside the sampled tokens' own): row -> (logprob, [(token, logprob)]
+        cut down to that row's top_logprobs)."""
+        if lp is None:
+            return {}
+        rows, tops, chosen_lp, top_id, top_lp = lp
+        chosen_lp, top_id, top_lp = (chosen_lp.tolist(), top_id.tolist(),
+                                     top_lp.tolist())
+        return {i: (chosen_lp[j],
+                    [(t, p) for t, p in zip(top_id[j][:n], top_lp[j][:n])
+                     if t >= 0])
+                for j, (i, n) in enumerate(zip(rows, tops))}
 
     def _sample_device(self, logits: torch.Tensor,
                        reqs: List[GenRequest]) -> torch.Tensor:
@@ -939,19 +1014,19 @@ class ModelInstance:
             self._pf_pending = (logits, f_reqs)
             self._phase_mark("pf_sample_ms", t0)
             return
-        toks = self._sample(logits, f_reqs)  # host sync point
+        toks, lps = self._sample_lp(logits, f_reqs)  # host sync point
         self._phase_mark("pf_sample_ms", t0)
         self._ema("pf_cpu_ms", (time.thread_time() - c0) * 1000.0)
-        self._publish_prefill(f_reqs, toks)
+        self._publish_prefill(f_reqs, toks, lps)
 
-    def _publish_prefill(self, f_reqs: List[GenRequest], toks) -> None:
+    def _publish_prefill(self, f_reqs: List[GenRequest], toks, lps) -> None:
         """Hand each finished prefill its first token."""
         now = time.time()
         with self._lock:
-            for r, t in zip(f_reqs, toks):
+            for i, (r, t) in enumerate(zip(f_reqs, toks)):
                 if r.done.is_set():
                     continue  # failed/detached while deferred
-                r.add_token(int(t))
+                r.add_token(int(t), lps.get(i))
                 r.first_token_t = now
                 self._finish_or_run(r, int(t))
 
@@ -965,7 +1040,7 @@ class ModelInstance:
         if self._prefill_stream is not None:
             # order the sampling kernels after the side-stream producer
             torch.cuda.current_stream().wait_stream(self._prefill_stream)
-        self._publish_prefill(f_reqs, self._sample(logits, f_reqs))
+        self._publish_prefill(f_reqs, *self._sample_lp(logits, f_reqs))
 
     @staticmethod
     def _prefill_bucket(n: int) -> int:
@@ -1166,12 +1241,12 @@ class ModelInstance:
                 self._model_idx, [self.kvm.slot(s) for s, _t in plan],
                 [t for _s, t in plan]))
         logits = self._decode_exec(plan)
-        toks = self._sample(logits, reqs)
+        toks, lps = self._sample_lp(logits, reqs)
         self.decode_tokens += len(reqs)
         self.occupancy_acc += len(reqs) / max(1, self.max_decode_batch)
         with self._lock:
-            for r, t in zip(reqs, toks):
-                r.add_token(int(t))
+            for i, (r, t) in enumerate(zip(reqs, toks)):
+                r.add_token(int(t), lps.get(i))
                 self._finish_or_run(r, int(t))
 
     def _decode_exec(self, plan) -> torch.Tensor:
@@ -1261,12 +1336,14 @@ class ModelInstance:
 
     def _run_async_plan(self, plan: AsyncDecodePlan,
                         prev_sampled: Optional[torch.Tensor],
-                        seq_ids: Optional[List[str]] = None) -> torch.Tensor:
+                        seq_ids: Optional[List[str]] = None,
+                        lp_reqs: Optional[List[GenRequest]] = None):
         """One speculative decode step, the same on every rank: prepare
         pages, launch (carried-over rows fed from this rank's OWN previous
         device sample: identical logits => identical sample), sample
         on-device by the plan's rows, advance. No host sync. Rank 0 passes
-        the seq_ids it has; a worker finds them by slot."""
+        the seq_ids it has; a worker finds them by slot. Returns (sampled,
+        _launch_logprobs' result for rank 0's lp_reqs, else None)."""
         kvm = self.kvm
         if seq_ids is None:
             seq_ids = [kvm.seq_of_slot(s) for s in plan.slots]
@@ -1282,9 +1359,11 @@ class ModelInstance:
                                   torch.full_like(gathered, -1))
         sampled = self._sample_rows(logits, plan.temps, plan.tops, plan.seeds,
                                     plan.ext, pending)
+        lp = (self._launch_logprobs(logits, lp_reqs, sampled)
+              if lp_reqs is not None else None)
         kvm.advance_many(seq_ids)
         self.decode_tokens += len(seq_ids)
-        return sampled
+        return sampled, lp
 
     def _decode_async_worker(self, cmd: List[int]) -> None:
         """Worker half of the speculative decode step: rank 0's plan after
@@ -1292,7 +1371,7 @@ class ModelInstance:
         plan = wire.decode_async(cmd, self._take_ext_tail)
         self.kvm.rollback_many([self.kvm.seq_of_slot(s)
                                 for s in plan.rollbacks])
-        self._spec_worker = self._run_async_plan(plan, self._spec_worker)
+        self._spec_worker, _ = self._run_async_plan(plan, self._spec_worker)
 
     def _take_ext_tail(self) -> List[int]:
         tail, self._ext_tail = self._ext_tail, None
@@ -1765,7 +1844,7 @@ class LLMEngine:
         if n > 50:
             self.store.ltrim(hist_key, n - 50, -1)
         self.store.hset(f"agent:{agent_id}:metrics", "total_requests", b.requests)
-        return {
+        payload = {
             "response": text,
             "model": model,
             "trace_id": req.trace_id or None,
@@ -1773,6 +1852,20 @@ class LLMEngine:
             "ttft_s": (req.first_token_t - req.enq_t) if req.first_token_t else None,
             "e2e_s": (req.fin_t - req.enq_t) if req.fin_t else None,
         }
+        if req.logprobs:
+            payload["logprobs"] = [self._logprob_entry(inst, e)
+                                   for e in req.token_logprobs]
+        return payload
+
+    @staticmethod
+    def _logprob_entry(inst, e: Dict[str, Any]) -> Dict[str, Any]:
+        """A GenRequest.token_logprobs entry in its reply form: each token
+        id beside the tokenizer's decoding of that single id."""
+        def one(t):
+            return {"token": t["token"],
+                    "text": inst.tokenizer.decode([t["token"]]),
+                    "logprob": t["logprob"]}
+        return {**one(e), "top": [one(t) for t in e["top"]]}
 
     def chat(self, agent_id: str, message: str, **kwargs: Any) -> Dict[str, Any]:
         from ..wal import EngineUnavailable
@@ -1792,7 +1885,9 @@ class LLMEngine:
     def chat_stream(self, agent_id: str, message: str, **kwargs: Any):
         """Streaming chat: yields {"token", "text"} events as the scheduler
         produces tokens, then one final {"done": True, **payload} event —
-        the SSE data frames of the /chat?stream path. Token->text deltas
+        the SSE data frames of the /chat?stream path. With logprobs on, a
+        token event also carries that token's "logprob" and "top", and the
+        final event the whole "logprobs" list. Token->text deltas
         re-decode the full id list each step so multi-byte UTF-8 sequences
         only surface once complete."""
         from ..wal import EngineUnavailable
@@ -1810,6 +1905,7 @@ class LLMEngine:
                                                   stream=True)
         deadline = time.time() + timeout
         dec = inst.tokenizer.stream_decoder()
+        n_read = 0
         while True:
             try:
                 tok = req.stream_q.get(timeout=0.1)
@@ -1824,7 +1920,14 @@ class LLMEngine:
                 continue
             if tok is None:
                 break
-            yield {"token": int(tok), "text": dec.feed(int(tok))}
+            frame = {"token": int(tok), "text": dec.feed(int(tok))}
+            if req.logprobs:
+                # appended before the token was queued: index by the count
+                # of tokens read so far
+                e = self._logprob_entry(inst, req.token_logprobs[n_read])
+                frame["logprob"], frame["top"] = e["logprob"], e["top"]
+            n_read += 1
+            yield frame
         if req.error:
             raise EngineUnavailable(req.error)
         tail = dec.flush()  # a dangling partial byte sequence

@@ -231,6 +231,25 @@ def sample_ex(out, logits, temps, top_ps, seeds, top_ks, min_ps, reps, press,
     return out
 
 
+def token_logprobs(logits, rows, chosen, K: int):
+    """Raw logprobs of the sampled tokens and the top K (0..20) of each
+    requested row (semantics: reference.token_logprobs). logits bf16
+    [B, V], read in place; rows int32 [R] picks the rows, in any order;
+    chosen int64 [B] is the sampler's output. Returns (chosen_lp f32 [R],
+    top_id int32 [R, K], top_lp f32 [R, K]) on the logits' device; the
+    launch is asynchronous."""
+    mod = _dispatch("token_logprobs", logits)
+    if not mod:
+        return reference.token_logprobs(logits, rows, chosen, K)
+    R, K = rows.numel(), int(K)
+    dev = logits.device
+    chosen_lp = torch.empty(R, dtype=torch.float32, device=dev)
+    top_id = torch.empty(R, K, dtype=torch.int32, device=dev)
+    top_lp = torch.empty(R, K, dtype=torch.float32, device=dev)
+    mod.token_logprobs(chosen_lp, top_id, top_lp, logits, rows, chosen, K)
+    return chosen_lp, top_id, top_lp
+
+
 _ws_cache = {}
 _EMPTY_WS = {}
 SKINNY_DISABLED = os.environ.get("AGENTAINER_DISABLE_SKINNY", "0") == "1"

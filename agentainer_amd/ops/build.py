@@ -41,6 +41,7 @@ SOURCES = [
     "prefill_attn.hip",
     "sampling.hip",
     "sample_ex.hip",
+    "logprobs.hip",
     "skinny_gemm.hip",
     "lora.hip",
 ]

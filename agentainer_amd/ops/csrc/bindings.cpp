@@ -32,6 +32,9 @@ void sample_ex(torch::Tensor out, torch::Tensor logits, torch::Tensor ws,
                torch::Tensor edit_ptr, torch::Tensor edit_tok,
                torch::Tensor edit_cnt, torch::Tensor edit_bias,
                torch::Tensor pending_tok);
+void token_logprobs(torch::Tensor chosen_lp, torch::Tensor top_id,
+                    torch::Tensor top_lp, torch::Tensor logits,
+                    torch::Tensor rows, torch::Tensor chosen, long K);
 void gather_kv_pages(torch::Tensor dst, torch::Tensor k_cache,
                      torch::Tensor v_cache, torch::Tensor page_ids);
 void skinny_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
@@ -75,6 +78,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("topp_sample", &topp_sample, "temperature + top-p sampling per row");
   m.def("sample_ex", &sample_ex,
         "penalties + logit_bias + exact top-k/min-p/top-p sampling per row");
+  m.def("token_logprobs", &token_logprobs,
+        "log-softmax of the chosen token + exact top-K logprobs per row");
   m.def("gather_kv_pages", &gather_kv_pages, "pages -> host-shaped buffer");
   m.def("splitk_add_rmsnorm", &splitk_add_rmsnorm,
         "residual += bf16(sum_s ws[s]); rmsnorm");

@@ -280,6 +280,45 @@ def sample_ex(out: torch.Tensor, logits: torch.Tensor, ws, temps, top_ps,
         out[b] = int(ids[min(j, ids.numel() - 1)])
 
 
+TOP_LOGPROBS_MAX = 20
+
+
+def token_logprobs(logits: torch.Tensor, rows: torch.Tensor,
+                   chosen: torch.Tensor, K: int):
+    """Logprobs of the model's own distribution (temperature 1, no
+    penalties, bias or cuts), for the rows of bf16 logits [B, V] that the
+    int32 `rows` [R] names, in that order. Returns (chosen_lp f32 [R],
+    top_id int32 [R, K], top_lp f32 [R, K]).
+
+    For b = rows[r]: lp = l - max(l) - log(sum(exp(l - max(l)))) over the
+    logits widened to float, evaluated in float64 and rounded to f32 (this
+    form keeps a token 80 nats below the maximum finite). chosen_lp[r] is
+    lp[chosen[b]], inside the top K or not. top_id[r] holds the min(K, V)
+    tokens that come first in the total order (logit descending, id
+    ascending; logits compare as floats, so -0.0 ties with +0.0) and
+    top_lp[r] their logprobs; slots past V hold -1 and -inf."""
+    B, V = logits.shape
+    K = int(K)
+    assert 0 <= K <= TOP_LOGPROBS_MAX
+    R = rows.numel()
+    chosen_lp = torch.empty(R, dtype=torch.float32)
+    top_id = torch.full((R, K), -1, dtype=torch.int32)
+    top_lp = torch.full((R, K), float("-inf"), dtype=torch.float32)
+    n = min(K, V)
+    for r, b in enumerate(rows.tolist()):
+        l = logits[b].detach().cpu().to(torch.float64) + 0.0  # -0.0 -> +0.0
+        d = l - l.max()
+        lp = (d - d.exp().sum().log()).to(torch.float32)
+        chosen_lp[r] = lp[int(chosen[b])]
+        if n:
+            # a stable descending sort leaves equal logits in id order
+            ids = torch.sort(l, descending=True, stable=True).indices[:n]
+            top_id[r, :n] = ids.to(torch.int32)
+            top_lp[r, :n] = lp[ids]
+    dev = logits.device
+    return chosen_lp.to(dev), top_id.to(dev), top_lp.to(dev)
+
+
 def gather_kv_pages(dst: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, page_ids: torch.Tensor) -> None:
     n_kv = k_cache.size(1)
