@@ -18,6 +18,12 @@ Lifecycle mapping:
   detach   = drain + offload KV to pinned host (+ disk for restarts)
   chat     = enqueue -> scheduler -> response (greedy => deterministic, so
              at-least-once crash replay regenerates identical output)
+
+Beside this module (which re-exports what its callers import from it):
+  request.py   GenRequest, AgentBinding, the sampling controls' validation
+  sampling.py  logits -> (tokens, logprobs), stateless
+  decode.py    decode buckets with their staging, the speculative step
+  plan.py      the TP plan channel's wire format
 """
 
 from __future__ import annotations
@@ -27,7 +33,6 @@ import queue
 import threading
 import time
 import traceback
-from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Tuple
 
 import torch
@@ -35,17 +40,19 @@ import torch
 from .. import ops
 from .. import parallel as par
 from ..store import Store
-from .base import InvalidSampling, ModelNotFound
-from .kvcache import KVCacheManager, KVCheckpoint, OutOfPages
 from . import plan as wire
+from . import sampling
+from .base import InvalidSampling, ModelNotFound
+from .decode import DecodeBucket, SpecStep, bucket, prefill_bucket
+from .kvcache import KVCacheManager, KVCheckpoint, OutOfPages
 from .plan import (OP_BARRIER, OP_DECODE, OP_DECODE_ASYNC, OP_ROLLBACK,
                    AsyncDecodePlan)
+from .request import (DEFAULT_MAX_NEW, AgentBinding, GenRequest,
+                      parse_sampling_controls)
 from .tokenizer import ByteTokenizer
 from ..models.llama import (AttnMetadata, LLAMA_CONFIGS, LlamaConfig,
                             LlamaForCausalLM)
 from ..models.lora import LoraContext, LoraError, LoraPool, adapter_key
-
-DEFAULT_MAX_NEW = 64
 
 
 def _ema_next(ema: float, ms: float) -> float:
@@ -55,184 +62,6 @@ def _ema_next(ema: float, ms: float) -> float:
 
 class EngineDead(RuntimeError):
     pass
-
-
-@dataclass(eq=False)
-class GenRequest:
-    agent_id: str
-    prompt_tokens: List[int]
-    max_new: int
-    temperature: float
-    top_p: float
-    seed: int
-    done: threading.Event = field(default_factory=threading.Event)
-    generated: List[int] = field(default_factory=list)
-    error: Optional[str] = None
-    enq_t: float = 0.0
-    first_token_t: float = 0.0
-    fin_t: float = 0.0
-    trace_id: str = ""  # WAL request id — end-to-end tracing
-    # streaming: the scheduler puts each sampled token id here as it is
-    # produced, then None when the request finishes (SSE /chat path)
-    stream_q: Optional[Any] = None
-    # chunked prefill: tokens of the prompt already written to KV, and the
-    # length of the slice admitted for the CURRENT step (set by _admit)
-    prefill_pos: int = 0
-    slice_len: int = 0
-    # extended sampling controls (ops.sample_ex); a request with all of
-    # them at these off values keeps the greedy_sample / topp_sample path
-    top_k: int = 0
-    min_p: float = 0.0
-    repetition_penalty: float = 1.0
-    presence_penalty: float = 0.0
-    frequency_penalty: float = 0.0
-    logit_bias: Dict[int, float] = field(default_factory=dict)
-    # penalty state: ids of the prompt, and how often each id was
-    # generated (kept by add_token, wherever `generated` grows)
-    prompt_set: Optional[frozenset] = None
-    gen_counts: Dict[int, int] = field(default_factory=dict)
-    # logprobs of the model's own distribution (ops.token_logprobs): with
-    # `logprobs` on, token_logprobs holds one entry per generated token,
-    # {"token", "logprob", "top": [{"token", "logprob"}] * top_logprobs}
-    logprobs: bool = False
-    top_logprobs: int = 0
-    token_logprobs: List[Dict[str, Any]] = field(default_factory=list)
-
-    # whether any control above is on; fixed at construction so that the
-    # per-step routing check costs one attribute read per row
-    extended: bool = field(init=False, default=False)
-
-    def __post_init__(self):
-        if self.prompt_set is None:
-            self.prompt_set = frozenset(self.prompt_tokens)
-        self.extended = bool(
-            self.top_k > 0 or self.min_p > 0.0
-            or self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
-            or self.frequency_penalty != 0.0 or self.logit_bias)
-
-    def add_token(self, tok: int, lp: Optional[Tuple] = None) -> None:
-        """lp: a requesting row's (logprob, [(token, logprob), ...]) from
-        ModelInstance._fetch_logprobs."""
-        self.generated.append(tok)
-        self.gen_counts[tok] = self.gen_counts.get(tok, 0) + 1
-        if self.logprobs:
-            self.token_logprobs.append({
-                "token": tok, "logprob": lp[0],
-                "top": [{"token": t, "logprob": p} for t, p in lp[1]]})
-
-    def ext_spec(self) -> Optional[Tuple]:
-        """(top_k, min_p, rep, pres, freq, edits) for an extended request,
-        else None. edits lists each touched token once as
-        (token, 2 * count + in_prompt, bias); tokens that no active
-        control can change are left out."""
-        if not self.extended:
-            return None
-        toks = set(self.logit_bias)
-        if self.repetition_penalty != 1.0:
-            toks |= self.prompt_set
-        if (self.repetition_penalty != 1.0 or self.presence_penalty != 0.0
-                or self.frequency_penalty != 0.0):
-            toks.update(self.gen_counts)
-        edits = [(t, 2 * self.gen_counts.get(t, 0) + (t in self.prompt_set),
-                  self.logit_bias.get(t, 0.0)) for t in sorted(toks)]
-        return (self.top_k, self.min_p, self.repetition_penalty,
-                self.presence_penalty, self.frequency_penalty, edits)
-
-
-SAMPLING_TOP_K_MAX = 1024
-SAMPLING_MAX_BIASES = 300
-SAMPLING_TOP_LOGPROBS_MAX = 20  # ops.token_logprobs' K
-
-
-def parse_sampling_controls(sampling: Dict[str, Any], vocab: int) -> Dict[str, Any]:
-    """Validate the extended sampling keys of a merged sampling dict and
-    return them as GenRequest keyword arguments (`logprobs` and
-    `top_logprobs` only when logprobs are asked for). Raises ValueError on
-    an ill-typed or out-of-range value."""
-    def num(key, default, lo, hi, lo_open=False):
-        v = sampling.get(key, default)
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError(f"sampling.{key} must be a number, got {v!r}")
-        v = float(v)
-        if (v != v or abs(v) == float("inf") or v > hi or v < lo
-                or (lo_open and v <= lo)):
-            raise ValueError(f"sampling.{key}={v} out of range")
-        return v
-
-    top_k = sampling.get("top_k", 0)
-    if isinstance(top_k, bool) or not isinstance(top_k, int):
-        raise ValueError(f"sampling.top_k must be an integer, got {top_k!r}")
-    if not 0 <= top_k <= SAMPLING_TOP_K_MAX:
-        raise ValueError(
-            f"sampling.top_k={top_k} out of range [0, {SAMPLING_TOP_K_MAX}]")
-    raw = sampling.get("logit_bias") or {}
-    if not isinstance(raw, dict):
-        raise ValueError("sampling.logit_bias must be an object {token_id: bias}")
-    if len(raw) > SAMPLING_MAX_BIASES:
-        raise ValueError(f"sampling.logit_bias has {len(raw)} entries "
-                         f"(max {SAMPLING_MAX_BIASES})")
-    bias: Dict[int, float] = {}
-    for k, v in raw.items():
-        try:
-            t = int(k)
-        except (TypeError, ValueError):
-            raise ValueError(f"sampling.logit_bias key {k!r} is not a token id")
-        if isinstance(k, (bool, float)) or not 0 <= t < vocab:
-            raise ValueError(
-                f"sampling.logit_bias token id {k!r} outside [0, {vocab})")
-        if isinstance(v, bool) or not isinstance(v, (int, float)) \
-                or not -100.0 <= float(v) <= 100.0:
-            raise ValueError(
-                f"sampling.logit_bias[{k}]={v!r} outside [-100, 100]")
-        if t in bias:
-            raise ValueError(f"sampling.logit_bias token id {t} given twice")
-        bias[t] = float(v)
-    want_lp = sampling.get("logprobs", False)
-    if not isinstance(want_lp, bool):
-        raise ValueError(f"sampling.logprobs must be a boolean, got {want_lp!r}")
-    top_lp = sampling.get("top_logprobs", 0)
-    if isinstance(top_lp, bool) or not isinstance(top_lp, int):
-        raise ValueError(
-            f"sampling.top_logprobs must be an integer, got {top_lp!r}")
-    if not 0 <= top_lp <= SAMPLING_TOP_LOGPROBS_MAX:
-        raise ValueError(f"sampling.top_logprobs={top_lp} out of range "
-                         f"[0, {SAMPLING_TOP_LOGPROBS_MAX}]")
-    if top_lp and not want_lp:
-        raise ValueError("sampling.top_logprobs requires sampling.logprobs")
-    controls = dict(
-        top_k=top_k,
-        min_p=num("min_p", 0.0, 0.0, 1.0),
-        repetition_penalty=num("repetition_penalty", 1.0, 0.0,
-                               float("inf"), lo_open=True),
-        presence_penalty=num("presence_penalty", 0.0, -2.0, 2.0),
-        frequency_penalty=num("frequency_penalty", 0.0, -2.0, 2.0),
-        logit_bias=bias,
-    )
-    if want_lp:
-        controls.update(logprobs=True, top_logprobs=top_lp)
-    return controls
-
-
-@dataclass
-class AgentBinding:
-    agent: Any
-    model_name: str
-    seq_id: str
-    paused: bool = False
-    requests: int = 0
-    tokens: int = 0
-    # /clear: the next admitted request prefills onto a reset KV sequence
-    # (plan-mirrored to TP workers via needs_reset)
-    pending_reset: bool = False
-    queue: "queue.Queue[GenRequest]" = field(default_factory=queue.Queue)
-    active: Optional[GenRequest] = None
-    # whole-page token prefix shared with other agents (system prompt),
-    # None when the system prompt is shorter than one KV page
-    prefix_tokens: Optional[List[int]] = None
-    # LoRA adapter (canonical directory path) and its pool slot; "" / -1
-    # for a base-model agent
-    adapter: str = ""
-    adapter_slot: int = -1
 
 
 class ModelInstance:
@@ -378,15 +207,18 @@ class ModelInstance:
         # (flushed at the head of the next broadcast, any kind)
         self._pending_rb: List[int] = []
         self._phase_ms: Dict[str, float] = {}
+        # EMA of wall step time; None until the first step seeds it
+        self._step_ms_ema: Optional[float] = None
         # deferred prefill sample (async engines): (logits, final_reqs)
-        self._pf_pending: Optional[tuple] = None
+        self._pf_pending: Optional[
+            Tuple[torch.Tensor, List[GenRequest]]] = None
         # worker-side speculative mirror: previous step's device sample
         self._spec_worker: Optional[torch.Tensor] = None
         # worker-side: an extended-sampling tail too long for the plan
         # vector, sent ahead of its OP_DECODE_ASYNC (plan.encode_async)
         self._ext_tail: Optional[List[int]] = None
-        self._spec: Optional[Dict[str, Any]] = None
-        self._graphs: Dict[int, Dict[str, Any]] = {}
+        self._spec: Optional[SpecStep] = None
+        self._graphs: Dict[int, DecodeBucket] = {}
         # prefill runs on its own HIP stream so a prefill batch overlaps
         # the in-flight decode graph replay (prefill is MFMA-bound, decode
         # is HBM-bound — they share the chip well). Safe by construction:
@@ -529,7 +361,8 @@ class ModelInstance:
             if ran:  # EMA of wall step time (engine-side diagnostics)
                 dt = (time.time() - self._step_started) * 1000.0
                 self._step_ms_ema = _ema_next(
-                    getattr(self, "_step_ms_ema", dt), dt)
+                    dt if self._step_ms_ema is None else self._step_ms_ema,
+                    dt)
             self._step_started = None
             self.last_step_t = time.time()
             return ran
@@ -584,29 +417,20 @@ class ModelInstance:
         launched = None
         prev = self._spec
         if batch:
-            bucket = min(self._bucket(len(batch)), max(self.max_decode_batch, 1))
-            if len(batch) > bucket:
-                batch = batch[:bucket]
+            cap = self._bucket_size(len(batch))
+            if len(batch) > cap:
+                batch = batch[:cap]
                 self._rotate_running(batch)
             seq_ids = [self._bindings[r.agent_id].seq_id for r in batch]
-            pos = {id(r): i for i, r in enumerate(prev["reqs"])} if prev else {}
+            pos = {id(r): i for i, r in enumerate(prev.reqs)} if prev else {}
             idx = [pos.get(id(r), -1) for r in batch]
-            # effective sampling seed: a carried-over row has ONE unresolved
-            # token in flight ahead of this sample (generated is appended at
-            # resolve, one step later), so its counter runs one ahead of
-            # len(generated) — this keeps the sampled stream identical to
-            # the synchronous path's seed+len(generated) sequence
-            seeds_eff = [(r.seed + len(r.generated)
-                          + (1 if idx[i] >= 0 else 0)) & 0x7FFFFFFFFFFFFFFF
-                         for i, r in enumerate(batch)]
+            temps, tops, seeds, ext = sampling.request_rows(
+                batch, carried=[x >= 0 for x in idx])
             plan = AsyncDecodePlan(
                 slots=[self.kvm.slot(s) for s in seq_ids],
                 feed=[r.generated[-1] if idx[i] < 0 else -1
                       for i, r in enumerate(batch)],
-                prev_idx=idx, seeds=seeds_eff,
-                temps=[r.temperature for r in batch],
-                tops=[r.top_p for r in batch],
-                ext=self._ext_specs(batch),
+                prev_idx=idx, seeds=seeds, temps=temps, tops=tops, ext=ext,
                 rollbacks=self._take_rollbacks())
             if self.tp_size > 1 and self.tp_rank == 0:
                 # async plan: pending rollbacks + per-row feed/sample spec;
@@ -615,13 +439,9 @@ class ModelInstance:
                 par.send_ints(wire.encode_async(self._model_idx, self.name,
                                                 plan))
             sampled, lp = self._run_async_plan(
-                plan, prev["sampled"] if prev else None, seq_ids,
-                lp_reqs=batch)
+                plan, prev.sampled if prev else None, seq_ids, lp_reqs=batch)
             self.occupancy_acc += len(batch) / max(1, self.max_decode_batch)
-            # lp: the logprobs kernel's own output tensors (or None), not
-            # the graph's logits buffer that the next replay overwrites
-            launched = {"reqs": batch, "sampled": sampled, "invalid": set(),
-                        "logprobs": lp}
+            launched = SpecStep(batch, sampled, logprobs=lp)
         t0 = self._phase_mark("p1_launch_ms", t0)
         self._spec = launched
 
@@ -690,17 +510,18 @@ class ModelInstance:
                         self._pages_freed = True
                     self._pump_agent(b)
 
-    def _resolve_spec(self, prev, launched) -> None:
+    def _resolve_spec(self, prev: Optional[SpecStep],
+                      launched: Optional[SpecStep]) -> None:
         if prev is None:
             return
-        toks = prev["sampled"].tolist()
-        lps = self._fetch_logprobs(prev["logprobs"])
+        toks = prev.sampled.tolist()
+        lps = prev.logprobs.fetch() if prev.logprobs else {}
         rollback_seqs = []
         with self._lock:
-            lpos = ({id(r): i for i, r in enumerate(launched["reqs"])}
+            lpos = ({id(r): i for i, r in enumerate(launched.reqs)}
                     if launched else {})
-            for i, r in enumerate(prev["reqs"]):
-                if i in prev["invalid"] or r.done.is_set():
+            for i, r in enumerate(prev.reqs):
+                if i in prev.invalid or r.done.is_set():
                     # invalidated row, or the request died (detach) mid-flight
                     continue
                 t = int(toks[i])
@@ -711,7 +532,7 @@ class ModelInstance:
                     # for this row: mark invalid + roll back that append
                     j = lpos.get(id(r))
                     if j is not None:
-                        launched["invalid"].add(j)
+                        launched.invalid.add(j)
                         b = self._bindings.get(r.agent_id)
                         if b is not None:
                             rollback_seqs.append(b.seq_id)
@@ -799,135 +620,36 @@ class ModelInstance:
             budget -= req.slice_len
         return out
 
-    def _sample(self, logits: torch.Tensor, reqs: List[GenRequest]) -> List[int]:
-        return self._sample_device(logits, reqs).tolist()
+    # ---------- sampling: engine.sampling behind three stable names ----------
 
-    def _sample_lp(self, logits: torch.Tensor, reqs: List[GenRequest]):
-        """_sample, and each requesting row's logprobs as _fetch_logprobs
-        returns them. Without such a row this is _sample alone."""
-        if not any(r.logprobs for r in reqs):
-            return self._sample(logits, reqs), {}
-        sampled = self._sample_device(logits, reqs)
-        lp = self._launch_logprobs(logits, reqs, sampled)
-        return sampled.tolist(), self._fetch_logprobs(lp)
-
-    def _launch_logprobs(self, logits: torch.Tensor, reqs: List[GenRequest],
-                         sampled: torch.Tensor) -> Optional[Tuple]:
-        """ops.token_logprobs right behind the sampler, in its stream, over
-        the rows that ask, with K the largest top_logprobs among them.
-        Returns None (nothing launched or built) when no row asks, else
-        (rows, their top_logprobs, chosen_lp, top_id, top_lp) with the
-        three outputs still on the device. Rank 0 only: the kernel holds
-        no collective and only rank 0 answers clients."""
-        rows = [i for i, r in enumerate(reqs) if r.logprobs]
-        if not rows:
-            return None
-        tops = [reqs[i].top_logprobs for i in rows]
-        rows_t = torch.tensor(rows, dtype=torch.int32).to(
-            logits.device, non_blocking=True)
-        lb = logits.to(torch.bfloat16).contiguous()  # as the samplers read it
-        return (rows, tops, *ops.token_logprobs(lb, rows_t, sampled, max(tops)))
-
-    @staticmethod
-    def _fetch_logprobs(lp: Optional[Tuple]) -> Dict[int, Tuple]:
-        """Bring a _launch_logprobs result to the host (a sync point, taken
-        beside the sampled tokens' own): row -> (logprob, [(token, logprob)]
-        cut down to that row's top_logprobs)."""
-        if lp is None:
-            return {}
-        rows, tops, chosen_lp, top_id, top_lp = lp
-        chosen_lp, top_id, top_lp = (chosen_lp.tolist(), top_id.tolist(),
-                                     top_lp.tolist())
-        return {i: (chosen_lp[j],
-                    [(t, p) for t, p in zip(top_id[j][:n], top_lp[j][:n])
-                     if t >= 0])
-                for j, (i, n) in enumerate(zip(rows, tops))}
+    def _sample_device_params(self, logits: torch.Tensor, temps: List[float],
+                              tops: List[float], seeds: List[int],
+                              ext=None, pending=None) -> torch.Tensor:
+        """sampling.sample. Every sampler launch of the engine, on rank 0
+        and on TP workers, goes through this name, looked up on the
+        instance, and with exactly these four positional arguments when no
+        row is extended: a measuring tool may wrap it."""
+        return sampling.sample(logits, temps, tops, seeds, ext, pending)
 
     def _sample_device(self, logits: torch.Tensor,
                        reqs: List[GenRequest]) -> torch.Tensor:
-        return self._sample_rows(
-            logits,
-            [r.temperature for r in reqs],
-            [r.top_p for r in reqs],
-            [(r.seed + len(r.generated)) & 0x7FFFFFFFFFFFFFFF for r in reqs],
-            self._ext_specs(reqs), None)
-
-    def _sample_rows(self, logits, temps_l, tops_l, seeds_l, ext, pending):
-        """_sample_device_params, called exactly as before extended
-        sampling existed whenever no row is extended."""
+        temps, tops, seeds, ext = sampling.request_rows(reqs)
         if ext is None:
-            return self._sample_device_params(logits, temps_l, tops_l, seeds_l)
-        return self._sample_device_params(logits, temps_l, tops_l, seeds_l,
-                                          ext=ext, pending=pending)
+            return self._sample_device_params(logits, temps, tops, seeds)
+        return self._sample_device_params(logits, temps, tops, seeds, ext=ext)
 
-    @staticmethod
-    def _ext_specs(reqs: List[GenRequest]) -> Optional[List[Optional[Tuple]]]:
-        """Per-row GenRequest.ext_spec(), or None when no row is extended
-        (the common case: nothing is built)."""
-        if not any(r.extended for r in reqs):
-            return None
-        return [r.ext_spec() for r in reqs]
+    def _sample(self, logits: torch.Tensor, reqs: List[GenRequest]) -> List[int]:
+        return self._sample_device(logits, reqs).tolist()
 
-    def _sample_device_params(self, logits: torch.Tensor,
-                              temps_l: List[float], tops_l: List[float],
-                              seeds_l: List[int],
-                              ext: Optional[List[Optional[Tuple]]] = None,
-                              pending: Optional[torch.Tensor] = None,
-                              ) -> torch.Tensor:
-        """Param-vector core shared by rank 0 (from GenRequests) and TP
-        workers (from the async plan): given bitwise-identical logits and
-        the same (temp, top_p, effective-seed) rows, every rank samples
-        the same tokens.
-
-        ext[i], where not None, is row i's GenRequest.ext_spec(): such
-        rows, greedy or not, form a third group sampled by ops.sample_ex.
-        pending (device int64 [B], -1 = none) holds each row's token that
-        is still in flight on the device (async decode)."""
-        B = logits.size(0)
-        out = torch.empty(B, dtype=torch.long, device=logits.device)
-        ext_rows = ([i for i in range(B) if ext[i] is not None]
-                    if ext is not None else [])
-        plain = ([i for i in range(B) if ext[i] is None]
-                 if ext_rows else range(B))
-        greedy_rows = [i for i in plain if temps_l[i] <= 0.0]
-        samp_rows = [i for i in plain if temps_l[i] > 0.0]
-        lb = logits.to(torch.bfloat16).contiguous()
-        if ext_rows:
-            sub = torch.empty(len(ext_rows), dtype=torch.long,
-                              device=logits.device)
-            specs = [ext[i] for i in ext_rows]
-            whole = len(ext_rows) == B
-            pend = pending
-            if pend is not None and not whole:
-                pend = pend.index_select(0, torch.tensor(
-                    ext_rows, dtype=torch.long, device=logits.device))
-            ops.sample_ex(
-                sub, lb if whole else lb[ext_rows].contiguous(),
-                [temps_l[i] for i in ext_rows], [tops_l[i] for i in ext_rows],
-                [seeds_l[i] for i in ext_rows], [sp[0] for sp in specs],
-                [sp[1] for sp in specs], [sp[2] for sp in specs],
-                [sp[3] for sp in specs], [sp[4] for sp in specs],
-                [sp[5] for sp in specs], pending=pend)
-            out[ext_rows] = sub
-        if greedy_rows:
-            if len(greedy_rows) == B:
-                ops.greedy_sample(out, lb)
-            else:
-                sub = torch.empty(len(greedy_rows), dtype=torch.long,
-                                  device=logits.device)
-                ops.greedy_sample(sub, lb[greedy_rows].contiguous())
-                out[greedy_rows] = sub
-        if samp_rows:
-            sub = torch.empty(len(samp_rows), dtype=torch.long, device=logits.device)
-            temps = torch.tensor([temps_l[i] for i in samp_rows],
-                                 dtype=torch.float32, device=logits.device)
-            tps = torch.tensor([tops_l[i] for i in samp_rows],
-                               dtype=torch.float32, device=logits.device)
-            seeds = torch.tensor([seeds_l[i] for i in samp_rows],
-                                 dtype=torch.int64, device=logits.device)
-            ops.topp_sample(sub, lb[samp_rows].contiguous(), temps, tps, seeds)
-            out[samp_rows] = sub
-        return out
+    def _sample_host(self, logits: torch.Tensor, reqs: List[GenRequest]):
+        """(tokens, row -> logprobs) on the host: the synchronous paths'
+        sync point. Without a requesting row this is _sample alone."""
+        if not any(r.logprobs for r in reqs):
+            return self._sample(logits, reqs), {}
+        logits = sampling.bf16_rows(logits)  # once, for both kernels
+        sampled = self._sample_device(logits, reqs)
+        lp = sampling.launch_logprobs(logits, reqs, sampled)
+        return sampled.tolist(), lp.fetch()
 
     def _bcast(self, cmd):
         if self.tp_size > 1 and self.tp_rank == 0:
@@ -956,7 +678,7 @@ class ModelInstance:
         for r in reqs:
             b = self._bindings[r.agent_id]
             first = r.prefill_pos == 0
-            needs_reset = first and bool(getattr(r, "needs_reset", False))
+            needs_reset = first and r.needs_reset
             sl = r.slice_len or (len(r.prompt_tokens) - r.prefill_pos)
             tokens = r.prompt_tokens[r.prefill_pos:r.prefill_pos + sl]
             is_final = (r.prefill_pos + sl) == len(r.prompt_tokens)
@@ -1014,7 +736,7 @@ class ModelInstance:
             self._pf_pending = (logits, f_reqs)
             self._phase_mark("pf_sample_ms", t0)
             return
-        toks, lps = self._sample_lp(logits, f_reqs)  # host sync point
+        toks, lps = self._sample_host(logits, f_reqs)  # host sync point
         self._phase_mark("pf_sample_ms", t0)
         self._ema("pf_cpu_ms", (time.thread_time() - c0) * 1000.0)
         self._publish_prefill(f_reqs, toks, lps)
@@ -1040,22 +762,7 @@ class ModelInstance:
         if self._prefill_stream is not None:
             # order the sampling kernels after the side-stream producer
             torch.cuda.current_stream().wait_stream(self._prefill_stream)
-        self._publish_prefill(f_reqs, *self._sample_lp(logits, f_reqs))
-
-    @staticmethod
-    def _prefill_bucket(n: int) -> int:
-        """Round a prefill token count up to a small set of GEMM shapes.
-
-        hipBLASLt runs its (CPU-expensive) algorithm heuristic per NEW
-        problem shape; real-text prompts make nearly every prefill batch
-        a never-seen M, which measured as ~100 ms of pure CPU per prefill
-        under HTTP serving (tools/server_load.py engine_mode.pf_cpu_ms).
-        Bucketing M to powers of two keeps the library cache warm after
-        one occurrence of each bucket."""
-        b = 32
-        while b < n:
-            b <<= 1
-        return b
+        self._publish_prefill(f_reqs, *self._sample_host(logits, f_reqs))
 
     def _prefill_exec(self, plan) -> torch.Tensor:
         """Runs identically on every TP rank (plan = seq ids + tokens)."""
@@ -1091,7 +798,7 @@ class ModelInstance:
         # pad the token dimension to a bucketed GEMM shape: extra tokens
         # form one fake row whose K/V land in the reserved scratch page 0
         # and whose logits are never read (last_rows covers real rows only)
-        n_pad = (self._prefill_bucket(len(ids)) - len(ids)
+        n_pad = (prefill_bucket(len(ids)) - len(ids)
                  if self.is_gpu else 0)
         if n_pad > 0:
             PS = self.kvm.page_size
@@ -1183,53 +890,42 @@ class ModelInstance:
         kvm.dev_seq_lens.index_fill_(0, self._pad_slot_t, -1)
         return logits
 
-    @staticmethod
-    def _bucket(n: int) -> int:
-        b = 1
-        while b < n:
-            b <<= 1
-        return b
+    def _bucket_size(self, n: int) -> int:
+        """The decode bucket that n rows run in (it holds fewer than n when
+        n exceeds the decode batch cap)."""
+        return min(bucket(n), max(self.max_decode_batch, 1))
 
-    def _get_graph(self, bucket: int) -> Dict[str, Any]:
-        entry = self._graphs.get(bucket)
+    def _get_graph(self, size: int) -> DecodeBucket:
+        entry = self._graphs.get(size)
         if entry is not None:
             return entry
-        dev = self.device
-        rows = torch.full((bucket,), self._pad_slot, dtype=torch.long, device=dev)
-        ids = torch.zeros(bucket, dtype=torch.long, device=dev)
-        inc = torch.ones(bucket, dtype=torch.int32, device=dev)
-        rows_pin = torch.full((bucket,), self._pad_slot, dtype=torch.long,
-                              pin_memory=self.is_gpu)
-        ids_pin = torch.zeros(bucket, dtype=torch.long, pin_memory=self.is_gpu)
-        entry = {"rows": rows, "ids": ids, "inc": inc, "rows_pin": rows_pin,
-                 "ids_pin": ids_pin, "graph": None, "logits": None}
+        entry = DecodeBucket.alloc(size, self._pad_slot, self.device)
         if self.use_graph:
             try:
                 for _ in range(2):  # warmup before capture (also exercises
-                    self._device_decode_fwd(rows, ids, inc)  # RCCL comms)
+                    self._device_decode_fwd(  # RCCL comms)
+                        entry.rows, entry.ids, entry.inc)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    entry["logits"] = self._device_decode_fwd(rows, ids, inc)
-                entry["graph"] = g
+                    entry.logits = self._device_decode_fwd(
+                        entry.rows, entry.ids, entry.inc)
+                entry.graph = g
             except Exception:
                 # e.g. an RCCL build that rejects capture: run eager. Every
                 # rank executes identical code, so the fallback is lockstep.
                 traceback.print_exc()
                 self.use_graph = False
                 self.async_decode = False
-                entry["graph"] = None
-                entry["logits"] = None
+                entry.graph = None
+                entry.logits = None
                 torch.cuda.synchronize()
-        self._graphs[bucket] = entry
+        self._graphs[size] = entry
         return entry
 
     def _decode(self, reqs: List[GenRequest]):
-        B0 = len(reqs)
         if self.dev_decode:
-            bucket = min(self._bucket(B0), max(self.max_decode_batch, 1))
-            if bucket < B0:
-                reqs = reqs[:bucket]
+            reqs = reqs[:self._bucket_size(len(reqs))]
         plan = [(self._bindings[r.agent_id].seq_id, r.generated[-1])
                 for r in reqs]
         if self.tp_size > 1 and self.tp_rank == 0:
@@ -1241,7 +937,7 @@ class ModelInstance:
                 self._model_idx, [self.kvm.slot(s) for s, _t in plan],
                 [t for _s, t in plan]))
         logits = self._decode_exec(plan)
-        toks, lps = self._sample_lp(logits, reqs)
+        toks, lps = self._sample_host(logits, reqs)
         self.decode_tokens += len(reqs)
         self.occupancy_acc += len(reqs) / max(1, self.max_decode_batch)
         with self._lock:
@@ -1295,28 +991,10 @@ class ModelInstance:
         prev_sampled (the previous step's device sample). Returns
         (logits[:B], carried): carried is None or the (mask, gathered) of
         that device-side feed, which the sampler's `pending` is built from.
-        ids_full keeps the synchronous path's copy of the pad rows' stale
-        ids: eager Mixtral at 65+ rows shapes its expert GEMMs by them."""
+        ids_full: see DecodeBucket.stage."""
         B = len(slots)
-        entry = self._get_graph(
-            min(self._bucket(B), max(self.max_decode_batch, 1)))
-        # the PREVIOUS step's non-blocking H2D copies read these pinned
-        # staging buffers; wait for that DMA before rewriting them (a
-        # torn read would feed wrong slots/tokens into the graph)
-        ev = entry.get("h2d_ev") if self.is_gpu else None
-        if ev is not None:
-            ev.synchronize()
-        entry["rows_pin"][:B] = torch.tensor(slots, dtype=torch.long)
-        entry["rows_pin"][B:] = self._pad_slot
-        entry["rows"].copy_(entry["rows_pin"], non_blocking=True)
-        entry["ids_pin"][:B] = torch.tensor([max(t, 0) for t in feed],
-                                            dtype=torch.long)
-        n = None if ids_full else B
-        entry["ids"][:n].copy_(entry["ids_pin"][:n], non_blocking=True)
-        if self.is_gpu:
-            if ev is None:
-                ev = entry["h2d_ev"] = torch.cuda.Event()
-            ev.record()
+        entry = self._get_graph(self._bucket_size(B))
+        entry.stage(slots, feed, self._pad_slot, ids_full)
         carried = None
         if prev_sampled is not None and any(x >= 0 for x in prev_idx):
             gidx = torch.tensor([max(x, 0) for x in prev_idx],
@@ -1324,15 +1002,14 @@ class ModelInstance:
             mask = torch.tensor([x >= 0 for x in prev_idx], dtype=torch.bool,
                                 device=self.device)
             gathered = prev_sampled.index_select(0, gidx)
-            entry["ids"][:B].copy_(
-                torch.where(mask, gathered, entry["ids"][:B]))
+            entry.ids[:B].copy_(torch.where(mask, gathered, entry.ids[:B]))
             carried = (mask, gathered)
-        if entry["graph"] is not None:
-            entry["graph"].replay()
-            return entry["logits"][:B], carried
+        if entry.graph is not None:
+            entry.graph.replay()
+            return entry.logits[:B], carried
         # eager fallback (capture failure / CPU emulation)
-        return self._device_decode_fwd(entry["rows"], entry["ids"],
-                                       entry["inc"])[:B], carried
+        return self._device_decode_fwd(entry.rows, entry.ids,
+                                       entry.inc)[:B], carried
 
     def _run_async_plan(self, plan: AsyncDecodePlan,
                         prev_sampled: Optional[torch.Tensor],
@@ -1343,23 +1020,31 @@ class ModelInstance:
         device sample: identical logits => identical sample), sample
         on-device by the plan's rows, advance. No host sync. Rank 0 passes
         the seq_ids it has; a worker finds them by slot. Returns (sampled,
-        _launch_logprobs' result for rank 0's lp_reqs, else None)."""
+        sampling.launch_logprobs' result for rank 0's lp_reqs, else None)."""
         kvm = self.kvm
         if seq_ids is None:
             seq_ids = [kvm.seq_of_slot(s) for s in plan.slots]
         kvm.decode_batch_prepare(seq_ids)  # same pages, deterministic
         logits, carried = self._launch_decode(plan.slots, plan.feed,
                                               plan.prev_idx, prev_sampled)
-        pending = None
-        if carried is not None and plan.ext is not None:
-            # a carried-over row's newest token is not in its host lists
-            # yet: the sampler counts it from the device
-            mask, gathered = carried
-            pending = torch.where(mask, gathered,
-                                  torch.full_like(gathered, -1))
-        sampled = self._sample_rows(logits, plan.temps, plan.tops, plan.seeds,
-                                    plan.ext, pending)
-        lp = (self._launch_logprobs(logits, lp_reqs, sampled)
+        # once, for the sampler and the logprobs kernel (the model's own
+        # bf16 rows come back as they are: no copy, no launch)
+        logits = sampling.bf16_rows(logits)
+        if plan.ext is None:
+            sampled = self._sample_device_params(logits, plan.temps,
+                                                 plan.tops, plan.seeds)
+        else:
+            pending = None
+            if carried is not None:
+                # a carried-over row's newest token is not in its host
+                # lists yet: the sampler counts it from the device
+                mask, gathered = carried
+                pending = torch.where(mask, gathered,
+                                      torch.full_like(gathered, -1))
+            sampled = self._sample_device_params(
+                logits, plan.temps, plan.tops, plan.seeds, ext=plan.ext,
+                pending=pending)
+        lp = (sampling.launch_logprobs(logits, lp_reqs, sampled)
               if lp_reqs is not None else None)
         kvm.advance_many(seq_ids)
         self.decode_tokens += len(seq_ids)
@@ -2017,7 +1702,7 @@ class LLMEngine:
                 "use_graph": inst.use_graph,
                 "async_decode": inst.async_decode,
                 "graph_buckets": sorted(inst._graphs.keys()),
-                "step_ms_ema": round(getattr(inst, "_step_ms_ema", 0.0), 3),
+                "step_ms_ema": round(inst._step_ms_ema or 0.0, 3),
                 "phase_ms": {k: round(v, 3)
                              for k, v in inst._phase_ms.items()},
                 "kv_pages_used": inst.kvm.used_pages,
@@ -2103,8 +1788,6 @@ class LLMEngine:
                 inst._prefill_exec(cmd[2])
             elif op == "ext_tail":
                 inst._ext_tail = cmd[2]  # consumed by the next async plan
-            elif op == "decode":
-                inst._decode_exec(cmd[2])
             elif op == "bind":
                 seq_id, has_ckpt = cmd[2], cmd[3]
                 ckpt = self._ckpts.pop(seq_id, None) if has_ckpt else None

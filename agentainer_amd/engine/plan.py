@@ -9,6 +9,7 @@ from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Tuple
 
 from .. import parallel as par
+from .request import ExtSpec
 
 OP_DECODE = 1   # [OP, model_idx, B, slot*B, token*B] — the per-step hot path
 OP_BARRIER = 2  # [OP] — timing fence (bench.py --tp)
@@ -48,7 +49,7 @@ class AsyncDecodePlan:
     seeds: List[int]
     temps: List[float]
     tops: List[float]
-    ext: Optional[List[Optional[Tuple]]] = None
+    ext: Optional[List[Optional[ExtSpec]]] = None
     rollbacks: List[int] = field(default_factory=list)
 
 
@@ -86,10 +87,10 @@ def encode_async(model_idx: int, name: str, p: AsyncDecodePlan) -> List[int]:
     rows = [i for i, sp in enumerate(p.ext) if sp is not None]
     tail = [len(rows)]
     for i in rows:
-        top_k, min_p, rep, pres, freq, edits = p.ext[i]
-        tail += [i, top_k, _f2i(min_p), _f2i(rep), _f2i(pres), _f2i(freq),
-                 _f2i(p.tops[i]), len(edits)]
-        for t, c, b in edits:
+        sp = ExtSpec(*p.ext[i])  # a plain tuple of its fields will do too
+        tail += [i, sp.top_k, _f2i(sp.min_p), _f2i(sp.rep), _f2i(sp.pres),
+                 _f2i(sp.freq), _f2i(p.tops[i]), len(sp.edits)]
+        for t, c, b in sp.edits:
             tail += [t, c, _f2i(b)]
     if 1 + len(vec) + len(tail) <= par.PLAN_CAP:
         vec += tail
@@ -122,5 +123,6 @@ def decode_async(cmd: List[int], take_tail: Callable) -> AsyncDecodePlan:
         edits = [(tail[off + 3 * k], tail[off + 3 * k + 1],
                   _i2f(tail[off + 3 * k + 2])) for k in range(n)]
         off += 3 * n
-        p.ext[i] = (top_k, _i2f(mp), _i2f(rep), _i2f(pres), _i2f(freq), edits)
+        p.ext[i] = ExtSpec(top_k=top_k, min_p=_i2f(mp), rep=_i2f(rep),
+                           pres=_i2f(pres), freq=_i2f(freq), edits=edits)
     return p

@@ -190,7 +190,7 @@ def test_mixed_adapters_in_one_captured_decode_batch(gpu_rt, tmp_path):
     # the LoRA nodes did not break capture, and the 4-row bucket replayed
     assert st["use_graph"] is True
     assert 4 in st["graph_buckets"]
-    assert inst._graphs[4]["graph"] is not None
+    assert inst._graphs[4].graph is not None
     assert st["lora"]["resident"] == [
         {"adapter": px, "slot": st["lora"]["resident"][0]["slot"],
          "refcount": 2}]

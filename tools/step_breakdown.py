@@ -42,22 +42,18 @@ def timed_step():
     kvm = inst.kvm
     t0 = time.time()
     B = len(reqs)
-    bucket = min(inst._bucket(B), max(inst.max_decode_batch, 1))
     row_ids = []
     for r in reqs:
         b = inst._bindings[r.agent_id]
         kvm.ensure_decode_page(b.seq_id)
         row_ids.append(kvm.slot(b.seq_id))
-    entry = inst._get_graph(bucket)
-    entry["rows_pin"][:B] = torch.tensor(row_ids, dtype=torch.long)
-    entry["rows_pin"][B:] = inst._pad_slot
-    entry["ids_pin"][:B] = torch.tensor([r.generated[-1] for r in reqs], dtype=torch.long)
-    entry["rows"].copy_(entry["rows_pin"], non_blocking=True)
-    entry["ids"].copy_(entry["ids_pin"], non_blocking=True)
+    entry = inst._get_graph(inst._bucket_size(B))
+    entry.stage(row_ids, [r.generated[-1] for r in reqs], inst._pad_slot,
+                ids_full=True)
     torch.cuda.synchronize(); t1 = time.time()
-    entry["graph"].replay()
+    entry.graph.replay()
     torch.cuda.synchronize(); t2 = time.time()
-    logits = entry["logits"][:B]
+    logits = entry.logits[:B]
     toks = orig_sample(logits, reqs)
     torch.cuda.synchronize(); t3 = time.time()
     with inst._lock:
